@@ -80,6 +80,77 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+# --dump-outputs: at most this many requests / txns of a step's result are written (a fixed, seeded sample of a
+# larger one), which keeps a dump far below 64 MB
+DUMP_SAMPLE = 65536
+DUMP_SEED = 0xACC0DD09
+
+
+def dump_sample(n):
+    """The indices --dump-outputs writes of an n-row result: all of them, or a fixed seeded sample (ascending)."""
+    if n <= DUMP_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False)).astype(np.int64)
+
+
+def dump_arrays(out_dir, arrays):
+    """Write {name: array} as out_dir/<name>.npy in float64 (every value written is an integer below 2^53)."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = written = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        path = os.path.join(out_dir, name + ".npy")
+        if a.size == 0:
+            # no empty file (e.g. the columns of a map without deps: its all-zero offsets are written), nor an
+            # earlier dump's file of that name
+            if os.path.exists(path):
+                os.remove(path)
+            continue
+        total += a.nbytes
+        written += 1
+        np.save(path, a)
+    if total > 64 << 20:
+        raise SystemExit("--dump-outputs: %d bytes written, more than 64 MB" % total)
+    log("dumped %d arrays (%d bytes) to %s" % (written, total, out_dir))
+
+
+def dump_deps(out_dir, store, res, stats):
+    """The PartialDeps of the last timed step as its caller reads them from the device result `res` (through the
+    regions under AD_REGIONS, else from the packed arrays): for a fixed sample of the requests, per map the CSR
+    columns of accord_deps.h's ad_deps_result re-based to the sample (keys / range ids, txnId indices into the
+    store's dictionary, keysToTxnIds, each with its per-request offsets), plus the sampled request indices and the
+    whole batch's per-map totals."""
+    n = int(res.n_txns)
+    idx = dump_sample(n)
+    if not res.keys[0]:
+        raw = store._regions_raw(res, idx)
+    else:
+        raw = []
+        for m in range(A.NMAPS):
+            cols = []
+            for off_p, arr_p, dt in ((res.keys_off[m], res.keys[m], np.int64), (res.txn_off[m], res.txns[m], np.uint32),
+                                     (res.k2t_off[m], res.k2t[m], np.int32)):
+                o = store._d2h(off_p, n + 1, np.uint64).astype(np.int64)
+                arr = store._d2h(arr_p, int(o[-1]), dt)
+                cnt = o[idx + 1] - o[idx]
+                no = np.zeros(len(idx) + 1, np.int64)
+                no[1:] = np.cumsum(cnt)
+                cols += [no, arr[np.repeat(o[idx] - no[:-1], cnt) + np.arange(int(no[-1]))]]
+            raw.append(tuple(cols))
+    arrays = {"requests": idx,
+              "totals": np.array([stats["n_pairs"][:3], stats["n_unique"][:3], stats["n_keys"][:3]], np.int64)}
+    for m, cols in enumerate(raw):
+        for name, a in zip(("keys_off", "keys", "txn_off", "txns", "k2t_off", "k2t"), cols):
+            if name == "keys":
+                # 64-bit keys as 32-bit halves (exact in float64): the high half signed, the low half unsigned
+                k = np.asarray(a, np.int64)
+                arrays["%s_keys_hi" % A.MAP_NAMES[m]] = k >> 32
+                arrays["%s_keys_lo" % A.MAP_NAMES[m]] = k & 0xFFFFFFFF
+            else:
+                arrays["%s_%s" % (A.MAP_NAMES[m], name)] = a
+    dump_arrays(out_dir, arrays)
+
+
 def measured_traffic(kernels, tag=None):
     """HBM bytes per launch summed over `kernels` from the newest committed PMC summary of this round
     (profiles/<PROFILE_ROUND>*_pmc.json, by name) that holds every one of them (FETCH_SIZE doubled for gfx950 as
@@ -341,6 +412,9 @@ def bench_levels(args, rank, world, local, dev):
     elapsed = time.perf_counter() - t_start
     ms /= max(args.steps, 1)
     pairs = int(g.key_off[-1])
+    if args.dump_outputs:
+        idx = dump_sample(len(g.kind))
+        dump_arrays(args.dump_outputs, {"txns": idx, "levels": out[torch.from_numpy(idx).to(dev)].cpu().numpy()})
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=_red_dev(dev))
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -389,7 +463,7 @@ def bench_levels(args, rank, world, local, dev):
         "stages_ms": {names[0]: round(float(ms[0]), 4), names[1]: round(float(ms[1]), 4)},
         "levels": stats["n_levels"], "edges": stats["n_edges"], "leveling_launches_per_step": launches / max(args.steps, 1),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.cpu_legs:
         res["cpu_baseline"] = cpu_baseline_levels(g, args.cpu_budget)
     if rank == 0:
         print(json.dumps(res), flush=True)
@@ -446,11 +520,48 @@ def bench_ranges(args, rank, world, local, dev):
     qdev, keep = native.device_queries(w.queries, dev)
     sp = torch.cuda.current_stream(dev).cuda_stream
     regions = args.output == "regions"     # the headline's output contract (AD_REGIONS) unless --output packed
-    elapsed, all_stats = _timed_steps(args, world, dev, lambda: store.deps_batch_device(qdev, sp, regions=regions)[1])
+    last = {}
+
+    def step():
+        last["res"], st = store.deps_batch_device(qdev, sp, regions=regions)
+        return st
+    elapsed, all_stats = _timed_steps(args, world, dev, step)
     stats = all_stats[-1]
     ms = np.mean([st["ms_stage"] for st in all_stats], axis=0)
     pairs = _sum_over_ranks(world, dev, w.queries.n_probes)
+    ms_per_step = 1000.0 * elapsed / max(args.steps, 1)
+    if args.dump_outputs:
+        dump_deps(args.dump_outputs, store, last["res"], stats)
+    res = {
+        "metric": METRIC, "value": pairs / (ms_per_step / 1000.0), "unit": "txn-key pairs/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+        "config": {"workload": "config4: %d txns x 4 keys vs %d range commands + %d-entry CommandsForKey history, "
+                               "SNAPSHOT%s" % (len(w.queries), len(w.cmds.txn), w.cfk.n_entries,
+                                               ", one replica per GPU" if world > 1 else ""),
+                   "txns_per_step": len(w.queries) * world, "txn_key_pairs_per_step": pairs,
+                   "parallelism": "replicas x%d" % world,
+                   "output": "regions (AD_REGIONS)" if regions else "packed arrays (request order)"},
+        "pairs_out": {A.MAP_NAMES[m]: int(stats["n_pairs"][m]) for m in range(3)},
+    }
+    if args.full:
+        res.update(ranges_extras(store, qdev, sp, regions, w, stats, ms))
+    if w.queries.range_off is not None:
+        res["config"]["range_requests"] = int(np.count_nonzero(np.diff(w.queries.range_off.astype(np.int64))))
+    if rank == 0 and world == 1 and args.cpu_legs:
+        res["cpu_baseline"] = cpu_baseline(w, args.cpu_budget)
+    if rank == 0:
+        print(json.dumps(res), flush=True)
+    store.close()
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def ranges_extras(store, qdev, sp, regions, w, stats, ms):
+    """--full of bench_ranges, from runs of their own after the timed steps: the other output layout's time, the
+    per-kernel split and the roofline of the resolve stages."""
     other = "packed" if regions else "regions"
+    dev = torch.device("cuda", torch.cuda.current_device())
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(5):
@@ -465,7 +576,6 @@ def bench_ranges(args, rank, world, local, dev):
             split_ms += np.array(store.deps_batch_device(qdev, sp, regions=regions)[1]["ms_stage"][:7]) / 3
     finally:
         del os.environ["AD_STAGE_EVENTS"]
-    ms_per_step = 1000.0 * elapsed / max(args.steps, 1)
     heads = sum(stats["n_keys"])
     out_bytes = 8 * heads + 4 * (heads + sum(stats["n_pairs"])) + 4 * sum(stats["n_unique"])
     n_rent = int(w.cmds.range_off[-1])
@@ -477,16 +587,7 @@ def bench_ranges(args, rank, world, local, dev):
     achieved = alg / (res_ms / 1000.0) / 1e9 if res_ms > 0 else 0.0
     res_kernels = resolve_kernels(stats, split_ms)
     traffic, src = measured_traffic(res_kernels, "config4")
-    res = {
-        "metric": METRIC, "value": pairs / (ms_per_step / 1000.0), "unit": "txn-key pairs/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
-        "config": {"workload": "config4: %d txns x 4 keys vs %d range commands + %d-entry CommandsForKey history, "
-                               "SNAPSHOT%s" % (len(w.queries), len(w.cmds.txn), w.cfk.n_entries,
-                                               ", one replica per GPU" if world > 1 else ""),
-                   "txns_per_step": len(w.queries) * world, "txn_key_pairs_per_step": pairs,
-                   "parallelism": "replicas x%d" % world,
-                   "output": "regions (AD_REGIONS)" if regions else "packed arrays (request order)"},
+    return {
         "%s_ms_per_step" % other: other_ms,
         "roofline": {"bound": "hbm", "kernel": " + ".join(res_kernels), "achieved": achieved, "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": src,
@@ -494,17 +595,7 @@ def bench_ranges(args, rank, world, local, dev):
         "stages_ms": {STAGES[i]: round(float(split_ms[i]), 4) for i in range(7)},
         "stages_note": "per-kernel split from 3 steps after the timed region (AD_STAGE_EVENTS=1); resolve %.4f ms "
                        "per timed step" % res_ms,
-        "pairs_out": {A.MAP_NAMES[m]: int(stats["n_pairs"][m]) for m in range(3)},
     }
-    if w.queries.range_off is not None:
-        res["config"]["range_requests"] = int(np.count_nonzero(np.diff(w.queries.range_off.astype(np.int64))))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        res["cpu_baseline"] = cpu_baseline(w, args.cpu_budget)
-    if rank == 0:
-        print(json.dumps(res), flush=True)
-    store.close()
-    if world > 1:
-        dist.destroy_process_group()
 
 
 def bench_preaccept(args, rank, world, local, dev):
@@ -527,6 +618,15 @@ def bench_preaccept(args, rank, world, local, dev):
     pairs = _sum_over_ranks(world, dev, w.queries.n_probes)
     ms_per_step = 1000.0 * elapsed / max(args.steps, 1)
     kernel_ms = float(np.mean([x["ms_device"] for x in all_stats]))
+    if args.dump_outputs:
+        # the proposals of a fixed sample of the requests: the 64-bit words as 32-bit halves (exact in float64)
+        idx = torch.from_numpy(dump_sample(n)).to(dev)
+        o = {k: v[idx].cpu().numpy() for k, v in out.items()}
+        arrays = {"requests": idx.cpu().numpy(), "node": o["node"], "flags": o["flags"]}
+        for k in ("msb", "lsb"):
+            u = o[k].view(np.uint64)
+            arrays[k + "_hi"], arrays[k + "_lo"] = u >> np.uint64(32), u & np.uint64(0xFFFFFFFF)
+        dump_arrays(args.dump_outputs, arrays)
     # algorithmic bytes: request inputs (txnId 20 B + key_off 8 B + 8 B per key), the map once
     # (8 B start + 20 B value + 1 B present per interval), outputs 21 B per request
     alg = 28 * n + 8 * w.queries.n_probes + 29 * len(mc) + 21 * n
@@ -542,7 +642,7 @@ def bench_preaccept(args, rank, world, local, dev):
                      "frac": achieved / HBM_PEAK_GBS, "traffic": None, "algorithmic_bytes_per_launch": alg,
                      "launch_ms": kernel_ms},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.cpu_legs:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import pyoracle
         m = min(n, 200_000)
@@ -622,7 +722,7 @@ def bench_union(args, rank, world, local, dev):
                      "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": None,
                      "algorithmic_bytes_per_launch": alg, "launch_ms": kernel_ms},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.cpu_legs:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import pyoracle
         m = min(n, 1_000)
@@ -710,7 +810,7 @@ def bench_recovery(args, rank, world, local, dev):
                       "pack": round(float(np.mean([x["ms_stage"][5] for x in all_stats])), 4)},
         "pairs_out": {A.MAP_NAMES[m]: int(stats["n_pairs"][m]) for m in range(3)},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.cpu_legs:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import pyoracle
         ost = pyoracle.OracleStore()
@@ -842,7 +942,7 @@ def bench_cfk_update(args, rank, world, local, dev):
         "inserted": [x["inserted"] for x in all_stats],
         "ingest_ms": ingest_ms,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.cpu_legs:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import cfk_update as U
         u0 = batches[0][0]
@@ -998,7 +1098,7 @@ def bench_sequential(args, rank, world, local, dev):
         "device_ms": stats["ms_device"], "ingest_ms": stats["ms_ingest"],
         "pairs_out": {A.MAP_NAMES[m]: int(stats["n_pairs"][m]) for m in range(3)},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.cpu_legs:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import pyoracle
         t0 = time.perf_counter()
@@ -1064,7 +1164,22 @@ def main():
     ap.add_argument("--dist-backend", default="nccl", choices=("nccl", "gloo"),
                     help="nccl (RCCL, one GPU per rank: the measured configuration); gloo: rehearsal of the "
                          "N>1 path on fewer GPUs (ranks share GPUs, the exchange is staged through host memory)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the CPU baseline and host-API legs (unless --no-cpu-baseline), the "
+                         "per-kernel split and roofline of the resolve, the other output layout's time. Off by "
+                         "default: a plain run sets up, warms up, times its steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64; a fixed "
+                         "seeded sample of a large result, under 64 MB in all). One GPU; deps (configs 2 and 4, "
+                         "without --exchange), --config 5 and --preaccept")
     args = ap.parse_args()
+    args.cpu_legs = args.full and not args.no_cpu_baseline
+    if args.dump_outputs:
+        if args.steps < 1:
+            raise SystemExit("--dump-outputs needs at least one timed step")
+        if (int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.exchange or args.config in (1, 3) or args.union or
+                args.recovery or args.cfk_update or args.steady):
+            raise SystemExit("--dump-outputs: one GPU; configs 2, 4, 5 and --preaccept only")
 
     global RED_DEV
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1226,27 +1341,9 @@ def bench_deps(args, rank, world, local, dev):
         xs["bytes_moved_all_ranks"] = int(p[1].item())
     ms_per_step = 1000.0 * elapsed / max(args.steps, 1)
     value = probes / (ms_per_step / 1000.0)
-    # the per-kernel split of the resolve (prepare, lean passes, general kernel) from three more steps
-    # after the timed region with the library's extra stage events on (AD_STAGE_EVENTS: each record
-    # idles the GPU ~4 us, so the timed steps carry only the resolve's start and end events)
-    split_ms = np.zeros(7)
-    os.environ["AD_STAGE_EVENTS"] = "1"
-    try:
-        for _ in range(3):
-            st_d, _, _ = step()
-            split_ms += np.array(st_d["ms_stage"][:7]) / 3
-    finally:
-        del os.environ["AD_STAGE_EVENTS"]
-    torch.cuda.synchronize(dev)
-
-    # roofline of the dominant kernel: the K1+K2 resolve of every request, which runs as lean pass 1,
-    # lean pass 2 and the general fused kernel on what they deferred (SURVEY §8(d) compulsory bytes
-    # of config 2 over the sum of their HIP-event times)
-    sbytes = stage_bytes(w, stats)
-    res_ms = float(sum(stage_ms[i] for i in RESOLVE_STAGES))
-    achieved = sbytes[0] / (res_ms / 1000.0) / 1e9 if res_ms > 0 else 0.0
-    res_kernels = resolve_kernels(stats, split_ms)
-    traffic, traffic_src = measured_traffic(res_kernels, "mix" if mix else "config%d" % cfg)   # the same workload's profile
+    if args.dump_outputs:
+        # the last timed step's result, before anything else runs on the store (its buffers belong to the store)
+        dump_deps(args.dump_outputs, store, last["res"], stats)
     xdesc = ""
     if world > 1:
         xdesc = (", per-store partials exchanged over RCCL inside libaccord_deps (ad_exchange) + K3 merge on the owning GPU"
@@ -1281,24 +1378,47 @@ def bench_deps(args, rank, world, local, dev):
         "data": "synthetic",
         "config": {"workload": workload, "txns_per_step": n_total, "txn_key_pairs_per_step": probes,
                    "parallelism": "store-per-gpu x%d" % world},
-        "roofline": {"bound": "hbm", "kernel": " + ".join(res_kernels), "achieved": achieved, "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                     "algorithmic_bytes_per_launch": sbytes[0], "launch_ms": res_ms},
-        "stages_ms": {STAGES[i]: round(float(split_ms[i]), 4) for i in range(7)},
-        "stages_note": "per-kernel split from 3 steps after the timed region (AD_STAGE_EVENTS=1); the timed steps "
-                       "record only the resolve's start and end (resolve %.4f ms per step)" % res_ms,
         "pairs_out": {A.MAP_NAMES[m]: int(stats["n_pairs"][m]) for m in range(3)},
         "deferred": {"lean_pass1_to_pass2": int(stats.get("n_lean_pass2", 0)),
                      "lean_to_general": int(stats.get("n_deferred_lean", 0)), "to_split": int(stats["n_deferred"])},
         "ingest_ms": ingest_ms,
     }
     if node_x is None and world == 1:
-        # the output contract of the timed steps, and the packed layout's cost beside it
+        # the output contract of the timed steps
         r = last["res"]
         out["config"]["output"] = ("regions (AD_REGIONS): each request's keyDeps / rangeDeps / directKeyDeps written once "
                                    "where the kernels build them, plus per-request sizes and packed offsets"
                                    if args.output == "regions" else "packed arrays (request order)")
         out["regions_bytes"] = {"in_use": int(r.regions_bytes), "payload": int(r.region_bytes)}
+    if args.full:
+        # the per-kernel split of the resolve (prepare, lean passes, general kernel) from three more steps
+        # after the timed region with the library's extra stage events on (AD_STAGE_EVENTS: each record
+        # idles the GPU ~4 us, so the timed steps carry only the resolve's start and end events)
+        split_ms = np.zeros(7)
+        os.environ["AD_STAGE_EVENTS"] = "1"
+        try:
+            for _ in range(3):
+                st_d, _, _ = step()
+                split_ms += np.array(st_d["ms_stage"][:7]) / 3
+        finally:
+            del os.environ["AD_STAGE_EVENTS"]
+        torch.cuda.synchronize(dev)
+        # roofline of the dominant kernel: the K1+K2 resolve of every request, which runs as lean pass 1,
+        # lean pass 2 and the general fused kernel on what they deferred (SURVEY §8(d) compulsory bytes
+        # of config 2 over the sum of their HIP-event times)
+        sbytes = stage_bytes(w, stats)
+        res_ms = float(sum(stage_ms[i] for i in RESOLVE_STAGES))
+        achieved = sbytes[0] / (res_ms / 1000.0) / 1e9 if res_ms > 0 else 0.0
+        res_kernels = resolve_kernels(stats, split_ms)
+        traffic, traffic_src = measured_traffic(res_kernels, "mix" if mix else "config%d" % cfg)   # the same workload's profile
+        out["roofline"] = {"bound": "hbm", "kernel": " + ".join(res_kernels), "achieved": achieved, "peak": HBM_PEAK_GBS,
+                           "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                           "algorithmic_bytes_per_launch": sbytes[0], "launch_ms": res_ms}
+        out["stages_ms"] = {STAGES[i]: round(float(split_ms[i]), 4) for i in range(7)}
+        out["stages_note"] = ("per-kernel split from 3 steps after the timed region (AD_STAGE_EVENTS=1); the timed steps "
+                              "record only the resolve's start and end (resolve %.4f ms per step)" % res_ms)
+    if args.full and node_x is None and world == 1:
+        # the packed layout's cost beside the timed steps' output contract
         other = "packed" if args.output == "regions" else "regions"
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
@@ -1307,12 +1427,12 @@ def bench_deps(args, rank, world, local, dev):
         torch.cuda.synchronize(dev)
         out["%s_ms_per_step" % other] = 1000.0 * (time.perf_counter() - t0) / 5
     if node_x is not None or world > 1:
-        out["stages_ms"]["merge (K3, owner)"] = round(merge_ms, 4)
+        out.setdefault("stages_ms", {})["merge (K3, owner)"] = round(merge_ms, 4)
         out["exchange"] = {"ms_export": round(xs["ms_export"], 4), "ms_move": round(xs["ms_move"], 4),
                            "ms_merge": round(xs["ms_merge"], 4), "ms_total": round(xs["ms_total"], 4),
                            "xgmi_bytes_per_step_rank0": int(xs["bytes_moved"]),
                            "xgmi_bytes_per_step_all_ranks": int(xs.get("bytes_moved_all_ranks", 0))}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and node_x is None:
+    if rank == 0 and world == 1 and args.cpu_legs and node_x is None:
         # the PCIe-inclusive rate a host caller sees through ad_deps_batch (host arrays in, packed
         # host CSR arrays out; outside the timed region, never `value`)
         # ad_deps_batch_into: caller-owned pinned host arrays, sliced so that copy-out overlaps the resolve

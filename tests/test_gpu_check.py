@@ -62,11 +62,22 @@ def _device_result(arrs, n):
     return r, keep
 
 
-def _first_nonempty(arrs, m, min_keys=2, min_ids=2):
-    ko, _, to, _, oo, _ = arrs[m]
+def _value_spans(k2t, p0, nk):
+    """(starts, ends) of each key's values within a request's keysToTxnIds at p0 (RelationMultiMap.java:245-257)."""
+    ends = k2t[p0:p0 + nk].astype(np.int64)
+    return np.concatenate([[nk], ends[:-1]]), ends
+
+
+def _first_nonempty(arrs, m, min_keys=2, min_ids=2, two_values=False):
+    """The first request with that many keys and ids in map m; two_values: one of whose keys holds two values."""
+    ko, _, to, _, oo, k2t = arrs[m]
     nk, nt = np.diff(ko.astype(np.int64)), np.diff(to.astype(np.int64))
     cand = np.nonzero((nk >= min_keys) & (nt >= min_ids))[0]
-    assert len(cand), "workload has no request with %d keys / %d ids in map %d" % (min_keys, min_ids, m)
+    if two_values:
+        spans = [_value_spans(k2t, int(oo[t]), int(nk[t])) for t in cand]
+        cand = np.array([t for t, (s, e) in zip(cand, spans) if np.any(e - s >= 2)], np.int64)
+    assert len(cand), "workload has no request with %d keys / %d ids%s in map %d" % (
+        min_keys, min_ids, " and a key with two values" if two_values else "", m)
     return int(cand[0])
 
 
@@ -103,7 +114,7 @@ def test_broken_results_are_flagged(resolved, fault):
     st, res, arrs = resolved
     a = [[x.copy() for x in mp] for mp in arrs]
     m = A.AD_MAP_KEY
-    t = _first_nonempty(a, m)
+    t = _first_nonempty(a, m, two_values=(fault == "dup_value"))
     ko, keys, to, tx, oo, k2t = a[m]
     k0, x0, p0 = int(ko[t]), int(to[t]), int(oo[t])
     nk, nt = int(ko[t + 1]) - k0, int(to[t + 1]) - x0
@@ -119,11 +130,8 @@ def test_broken_results_are_flagged(resolved, fault):
         k2t[p0 + nk - 1] -= 1
     elif fault == "dup_value":
         # a key holding two values gets its first one twice
-        ends = k2t[p0:p0 + nk].astype(np.int64)
-        starts = np.concatenate([[nk], ends[:-1]])
-        j = int(np.nonzero(ends - starts >= 2)[0][0]) if np.any(ends - starts >= 2) else None
-        if j is None:
-            pytest.skip("no key with two values")
+        starts, ends = _value_spans(k2t, p0, nk)
+        j = int(np.nonzero(ends - starts >= 2)[0][0])
         k2t[p0 + starts[j] + 1] = k2t[p0 + starts[j]]
     elif fault == "value_range":
         k2t[p0 + nk] = nt
