@@ -61,6 +61,11 @@ class Tids:
         return list(zip(self.msb.tolist(), self.lsb.tolist(), self.node.tolist()))
 
 
+def tid_order(t):
+    """Sort key of one (msb, lsb, node) tuple reproducing Timestamp.compareTo (Timestamp.java:208-217)."""
+    return (t[0], t[1] >> 16, t[1] & 0x1E, t[2])
+
+
 def make_timestamps(epoch, hlc, flags, node):
     """Timestamp(epoch, hlc, flags, node): msb = epoch<<15 | hlc>>>48, lsb = hlc<<16 | flags
     (Timestamp.java:81-89)."""
@@ -279,6 +284,57 @@ class Redundant:
         z = np.zeros(0, np.int64)
         z64 = np.zeros(0, np.uint64)
         return Redundant(z, z, z, z, Tids(z64, z64, np.zeros(0, np.int32)))
+
+    def entries(self):
+        """[(start, end, startEpoch, endEpoch, (msb, lsb, node))] in entry order."""
+        return list(zip(self.range_start.tolist(), self.range_end.tolist(), self.start_epoch.tolist(),
+                        self.end_epoch.tolist(), self.wm.tuples()))
+
+    @staticmethod
+    def from_entries(ents):
+        if not ents:
+            return Redundant.empty()
+        return Redundant(np.array([e[0] for e in ents], np.int64), np.array([e[1] for e in ents], np.int64),
+                         np.array([e[2] for e in ents], np.int64), np.array([e[3] for e in ents], np.int64),
+                         Tids(np.array([e[4][0] for e in ents], np.uint64), np.array([e[4][1] for e in ents], np.uint64),
+                              np.array([e[4][2] for e in ents], np.int32)))
+
+    @staticmethod
+    def merge(a, b):
+        """RedundantBefore.merge (RedundantBefore.java:375-377) over the fields this library carries:
+        ReducingIntervalMap.mergeIntervals walks the two maps' common refinement; a piece both hold takes
+        Entry.merge (:121-157) -- a's entry unchanged if a.startEpoch > b.endEpoch, b's if b.startEpoch > a.endEpoch
+        (:123-127), else max of the start epochs, min of the end epochs, max of shardAppliedOrInvalidatedBefore
+        (:129-142) --, a piece one holds takes that entry; each is sliced to its piece (Builder.slice, :473-479) and
+        touching pieces equal apart from their range are joined (tryMergeEqual, :488-498). Boundaries compare alike
+        under either inclusivity. A Java host passes ad_redundant_merge its OWN merged map: its equalsIgnoreRange
+        also compares locallyAppliedOrInvalidatedBefore, bootstrappedAt and staleUntilAtLeast, so it may keep apart
+        entries this restatement joins."""
+        ea, eb = a.entries(), b.entries()
+        cuts = sorted({x for e in ea + eb for x in e[:2]})
+        out, ia, ib = [], 0, 0
+        for s, e in zip(cuts, cuts[1:]):
+            while ia < len(ea) and ea[ia][1] <= s:
+                ia += 1
+            while ib < len(eb) and eb[ib][1] <= s:
+                ib += 1
+            x = ea[ia] if ia < len(ea) and ea[ia][0] <= s else None
+            y = eb[ib] if ib < len(eb) and eb[ib][0] <= s else None
+            if x is None and y is None:
+                continue
+            if x is None or y is None:
+                v = (x or y)[2:]
+            elif x[2] > y[3]:
+                v = x[2:]
+            elif y[2] > x[3]:
+                v = y[2:]
+            else:
+                v = (max(x[2], y[2]), min(x[3], y[3]), x[4] if tid_order(x[4]) >= tid_order(y[4]) else y[4])
+            if out and out[-1][1] == s and out[-1][2:] == v:
+                out[-1] = (out[-1][0], e) + v
+            else:
+                out.append((s, e) + tuple(v))
+        return Redundant.from_entries(out)
 
 
 @dataclass

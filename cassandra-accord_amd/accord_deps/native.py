@@ -30,7 +30,7 @@ EXPORTS = ("ad_abi_version", "ad_ctx_create", "ad_ctx_destroy", "ad_last_error",
            "ad_check_result_device", "ad_check_snapshot", "ad_cfk_prune", "ad_cfk_byid", "ad_cfk_missing",
            "ad_cfk_load_pruned", "ad_host_register", "ad_host_unregister", "ad_deps_batch_into",
            "ad_debug_guard_check", "ad_host_alloc", "ad_host_free", "ad_cfk_update_status",
-           "ad_slice_sets_load", "ad_redundant_advance", "ad_range_cmds_update")
+           "ad_slice_sets_load", "ad_redundant_advance", "ad_range_cmds_update", "ad_redundant_merge")
 
 
 class AccordDepsError(RuntimeError):
@@ -113,6 +113,7 @@ def lib():
         L.ad_check_result_device.argtypes = [C.c_void_p, C.POINTER(A.AdDepsResult), C.c_void_p, C.POINTER(C.c_uint64),
                                              C.POINTER(C.c_uint64)]
         L.ad_redundant_advance.argtypes = [C.c_void_p, C.POINTER(A.AdRedundantSoa), C.POINTER(A.AdStats)]
+        L.ad_redundant_merge.argtypes = [C.c_void_p, C.POINTER(A.AdRedundantSoa), C.POINTER(A.AdStats)]
         L.ad_range_cmds_update.argtypes = [C.c_void_p, C.POINTER(A.AdRangeCmdsSoa), C.POINTER(A.AdStats)]
         L.ad_cfk_prune.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int64, C.POINTER(C.c_uint64),
                                    C.POINTER(A.AdStats)]
@@ -306,6 +307,16 @@ class DeviceCommandStore:
         CommandsForKeys are truncated on the device. Returns stats (n_keys[0] entries removed, [1] keys changed)."""
         st = A.AdStats()
         self._check(lib().ad_redundant_advance(self.h, C.byref(redundant.soa()), C.byref(st)))
+        return stats_dict(st)
+
+    def redundant_merge(self, redundant):
+        """ad_redundant_merge: the store's whole RedundantBefore after a RedundantBefore.merge (model.Redundant.merge
+        for this library's fields; a Java host passes its own map) -- boundaries may change, no watermark may fall
+        back. The range part follows and the CommandsForKeys of the risen spans are truncated on the device. Returns
+        stats (n_keys[0] entries removed, [1] keys changed, [2] ids added, n_probes keys examined, ms_stage[1] the
+        range part refresh)."""
+        st = A.AdStats()
+        self._check(lib().ad_redundant_merge(self.h, C.byref(redundant.soa()), C.byref(st)))
         return stats_dict(st)
 
     def cfk_prune(self, keys=None, prune_interval=1, min_hlc_delta=0):

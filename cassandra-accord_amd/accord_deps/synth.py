@@ -13,7 +13,7 @@ All data is synthetic; key ordinals stand for Key.compareTo order (IntKey-like t
 import numpy as np
 
 from . import _abi as A
-from .model import (CfkSnapshot, Graph, Queries, RangeCommands, Redundant, Tids, Workload,
+from .model import (tid_order, CfkSnapshot, Graph, Queries, RangeCommands, Redundant, Tids, Workload,
                     make_timestamps, make_txn_ids)
 
 EXEC_NODE_BASE = 1 << 24        # executeAt node ids never collide with txnId node ids (1..16)
@@ -991,6 +991,71 @@ def advance_redundant(red, seed, step_frac=0.15, hist_hlc=None, frac=0.7):
     pick = lambda a, b: np.where(move, b, a)  # noqa: E731
     wm = Tids(pick(red.wm.msb, new.msb), pick(red.wm.lsb, new.lsb), pick(red.wm.node, new.node).astype(np.int32))
     return Redundant(red.range_start, red.range_end, red.start_epoch, red.end_epoch, wm)
+
+
+def merge_redundant(red, seed, mode="split", ranges=None, entry=None, hlc=None, step_frac=0.15, hist_hlc=None,
+                    lo=-520, hi=520, return_add=False):
+    """red after one RedundantBefore.merge(red, create(ranges, ...)) step (model.Redundant.merge): the addition
+    is one to three sub-ranges sharing one forward shardAppliedOrInvalidatedBefore and the epochs of the entries
+    it meets (RedundantBefore.create, RedundantBefore.java:357-373), above every watermark it covers, so that no
+    piece falls back -- what ad_redundant_merge accepts. `mode` picks the sub-ranges unless `ranges` gives them:
+      "split"  strictly inside entry `entry` (default: a random one at least 3 wide): one entry becomes three;
+      "join"   the lower of two touching entries with equal epochs, raised to its neighbour's watermark: they join;
+      "gap"    one to three stretches no entry holds, inside [lo, hi);
+      "wm"     exactly entry `entry`'s range: a watermark-only move;
+      "span"   from the first start to the last end: everything (gaps too) becomes one entry.
+    `hlc` fixes the new watermark's hlc (else up to step_frac of hist_hlc ticks above the covered ones). Returns
+    the merged Redundant (with return_add: and the addition)."""
+    rng = np.random.default_rng(seed)
+    ents = red.entries()
+    n = len(ents)
+    wm = None
+    if ranges is not None:
+        rs = [(int(a), int(b)) for a, b in ranges]
+    elif mode == "split":
+        wide = [i for i in range(n) if ents[i][1] - ents[i][0] >= 3]
+        i = int(entry) if entry is not None else int(rng.choice(wide))
+        s, e = ents[i][:2]
+        a = int(rng.integers(s + 1, e - 1))
+        rs = [(a, int(rng.integers(a + 1, e)))]
+    elif mode == "join":
+        pairs = [i for i in range(n - 1) if ents[i][1] == ents[i + 1][0] and ents[i][2:4] == ents[i + 1][2:4]
+                 and ents[i][4] != ents[i + 1][4]]
+        if not pairs:
+            raise ValueError("no touching entries with equal epochs to join")
+        i = int(rng.choice(pairs))
+        low, high = (i, i + 1) if tid_order(ents[i][4]) < tid_order(ents[i + 1][4]) else (i + 1, i)
+        rs, wm = [ents[low][:2]], ents[high][4]
+    elif mode == "gap":
+        edges = [lo] + [x for e in ents for x in e[:2]] + [hi]
+        gaps = [(edges[j], edges[j + 1]) for j in range(0, len(edges), 2) if edges[j + 1] - edges[j] >= 1]
+        pick = rng.choice(len(gaps), min(len(gaps), int(rng.integers(1, 4))), replace=False)
+        rs = []
+        for j in sorted(pick.tolist()):
+            s, e = gaps[j]
+            a = int(rng.integers(s, e))
+            rs.append((a, int(rng.integers(a + 1, e + 1))))
+    elif mode == "wm":
+        i = int(entry) if entry is not None else int(rng.integers(0, n))
+        rs = [ents[i][:2]]
+    elif mode == "span":
+        rs = [(ents[0][0], ents[-1][1])]
+    else:
+        raise ValueError(mode)
+    met = [e for e in ents if any(e[0] < b and a < e[1] for a, b in rs)]
+    e0, e1 = (met[0][2], met[0][3]) if met else (0, 1 << 40)
+    if wm is None:
+        old = Tids(np.array([e[4][0] for e in met], np.uint64), np.array([e[4][1] for e in met], np.uint64),
+                   np.array([e[4][2] for e in met], np.int32))
+        top = int(_hlc(old).max()) if len(old) else 0
+        ep = max([1] + [int(m >> 15) for m in old.msb.tolist()])
+        if hlc is None:
+            hlc = top + int(rng.integers(1, max(2, int((hist_hlc or top + 1000) * step_frac))))
+        t = make_txn_ids(ep, np.array([hlc], np.uint64), A.KIND_EXCLUSIVE_SYNC_POINT, int(rng.integers(1, 17)), domain=1)
+        wm = t.tuples()[0]
+    add = Redundant.from_entries([(a, b, e0, e1, wm) for a, b in rs])
+    merged = Redundant.merge(red, add)
+    return (merged, add) if return_add else merged
 
 
 def range_cmd_updates(cmds, seed, n, lo=-520, hi=520, epoch=1, hlc_hi=500, frac=(0.35, 0.25, 0.15, 0.25), max_width=120):

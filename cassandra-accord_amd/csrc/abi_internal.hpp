@@ -182,6 +182,7 @@ struct ad_ctx {
     double ms_ingest = 0;
     double ms_truncate = 0;         // RedundantBefore truncations since the last stats read (device time)
     uint64_t n_truncated = 0;       // entries they removed
+    uint64_t n_trunc_examined = 0;  // keys they examined
     uint64_t n_trunc_keys = 0;      // CommandsForKeys they changed
 
     // built snapshot
@@ -339,6 +340,7 @@ struct ad_ctx {
     // device ingest (ingest.hip): ad_cfk_load puts the snapshot's columns in HBM (raw_dev) and the
     // build derives everything there; the host's byId ids and dictionary copy follow on demand
     DevBuf d_adv_m, d_adv_l, d_adv_n, d_adv_rank;     // ad_redundant_advance: the new watermarks, their ranks
+    DevBuf d_rb_span;                                 // ad_redundant_merge: the risen spans (RbSpan)
     DevBuf d_in_seg, d_in_pruned, d_in_tm, d_in_tl, d_in_tn, d_in_em, d_in_el, d_in_en, d_in_xm, d_in_xl, d_in_xn, d_ing_rank;
     bool raw_dev = false;                            // d_in_* hold the loaded snapshot (no device update since)
     uint64_t raw_ne = 0;
@@ -427,7 +429,8 @@ uint64_t* rb_slot(ad_ctx* c);
 int build_snapshot(ad_ctx* c);
 int build_dict_buckets(ad_ctx* c, hipStream_t st);   // abi_snapshot.cpp: the sample level's bucket index
 // the snapshot truncated to the RedundantBefore it holds (SafeCommandStore.maybeTruncate, every key)
-int truncate_to_rb(ad_ctx* c);
+// spans (null: every key): only the keys inside these risen spans are examined (ad_redundant_merge)
+int truncate_to_rb(ad_ctx* c, const std::vector<adx::RbSpan>* spans = nullptr);
 // Range commands and RedundantBefore of a snapshot build (abi_snapshot.cpp): the stabbing index's cell ends,
 // whether it could be built, the range entries
 struct RangePart {
@@ -475,5 +478,7 @@ int cfk_update_follow(ad_ctx* c, const CfkUpdOut& o, int rc, hipStream_t st);
 // ids (host) joined to the device dictionary where it does not hold them; ranks[i] their member ranks (host
 // copies follow as after an update batch). ms: host-timed.
 int dict_ensure_ids(ad_ctx* c, const std::vector<Tid>& ids, std::vector<uint32_t>* ranks, uint64_t* n_new);
+// abi.cpp: the range part of a built snapshot rebuilt from the host registry and RedundantBefore
+int refresh_range_part(ad_ctx* c, uint64_t n_old, uint64_t* n_new_ids);
 
 }  // namespace adi

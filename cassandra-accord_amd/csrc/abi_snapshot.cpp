@@ -667,11 +667,13 @@ bool below_redundant(const ad_ctx* c, int64_t key, const Tid& t)
     return w && norm_cmp(norm(t), norm(*w)) < 0;
 }
 
-int truncate_to_rb(ad_ctx* c)
+int truncate_to_rb(ad_ctx* c, const std::vector<RbSpan>* spans)
 {
     bool any = false;
     for (const Tid& t : c->rb.wm) any = any || tid_gt_none(t);
-    if (!any || !c->ds.n_keys) return 0;
+    if (!any || !c->ds.n_keys || (spans && spans->empty())) return 0;
+    if (spans)
+        if (int rc = upload(c, c->d_rb_span, *spans)) return rc;
     auto& K = c->cfk;
     const uint64_t nk = c->ds.n_keys;
     // host-held missing() lists follow on the host (their ids need not be in the dictionary); the
@@ -703,13 +705,15 @@ int truncate_to_rb(ad_ctx* c)
     CfkTruncOut o;
     std::string e;
     const int rc = run_cfk_truncate(c->cu, c->ds, d, &b, cfk_need_bufs, c, grow, c->stream, &o, &e, &miss,
-                                    host_lists ? pos.data() : nullptr);
+                                    host_lists ? pos.data() : nullptr, spans ? c->d_rb_span.as<RbSpan>() : nullptr,
+                                    spans ? spans->size() : 0);
     if (rc)
     {
         c->host_stale = true;
         c->dirty = true;
         return c->fail(rc, "RedundantBefore truncation: %s", e.c_str());
     }
+    c->n_trunc_examined += o.n_examined;
     c->ms_truncate += o.ms_total;
     c->n_truncated += o.n_removed;
     c->n_trunc_keys += o.n_keys;

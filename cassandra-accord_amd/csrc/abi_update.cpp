@@ -583,6 +583,7 @@ int dict_ensure_ids(ad_ctx* c, const std::vector<Tid>& ids, std::vector<uint32_t
                        c->d_kcell.p ? c->d_kcell.as<uint32_t>() : nullptr};
     // the host's per-entry copies are rebuilt from the device on demand after a merge (it remaps every rank): no
     // host remap of them here
+    const bool aligned = !c->host_moved || c->host_ingested;
     if (!c->host_moved)
     {
         c->host_moved = true;
@@ -606,6 +607,8 @@ int dict_ensure_ids(ad_ctx* c, const std::vector<Tid>& ids, std::vector<uint32_t
         c->dirty = true;        // rebuilt from the host copies at the next use
         return c->fail(rc, "id dictionary growth: %s", e.c_str());
     }
+    // a merge's follow-up marks the entries as moved (an update batch's insertions); here only ranks changed
+    if (aligned) c->host_ingested = true;
     HIPCHK(c, d2h(ranks->data(), c->d_adv_rank.p, 4 * nx, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *n_new = o.n_new_ids;
@@ -939,6 +942,141 @@ int ad_redundant_advance(ad_ctx* c, const ad_redundant_soa* in, ad_stats* stats)
         stats->n_keys[0] = c->n_truncated;
         stats->n_keys[1] = c->n_trunc_keys;
         stats->n_keys[2] = n_new;
+    }
+    return AD_OK;
+}
+
+// ---- RedundantBefore merged in place: the entry boundaries may change (RedundantBefore.merge as
+// CommandStore.upsertRedundantBefore applies it, RedundantBefore.java:375-377; VERDICT r6 "what's missing" #1) ----
+int ad_redundant_merge(ad_ctx* c, const ad_redundant_soa* in, ad_stats* stats)
+{
+    if (!c || !in) return AD_E_INVAL;
+    auto& B = c->rb;
+    const uint64_t n = in->n, n0 = B.start.size();
+    const bool incl = c->cfg.range_start_inclusive != 0;
+    if (n && (!in->range_start || !in->range_end || !in->start_epoch || !in->end_epoch || !in->wm_msb || !in->wm_lsb ||
+              !in->wm_node))
+        return c->fail(AD_E_INVAL, "ad_redundant_merge: null arrays");
+    auto wm_of = [&](uint64_t i) { return Tid{in->wm_msb[i], in->wm_lsb[i], in->wm_node[i]}; };
+    for (uint64_t i = 0; i < n; ++i)
+    {
+        if (in->range_start[i] >= in->range_end[i])
+            return c->fail(AD_E_INVAL, "ad_redundant_merge: entry %llu's range is empty", (unsigned long long)i);
+        if (i && in->range_start[i] <= in->range_start[i - 1])
+            return c->fail(AD_E_INVAL, "ad_redundant_merge: entry %llu does not start above entry %llu (entries ascend)",
+                           (unsigned long long)i, (unsigned long long)(i - 1));
+        if (i && in->range_end[i - 1] > in->range_start[i])
+            return c->fail(AD_E_INVAL, "ad_redundant_merge: entries %llu and %llu overlap", (unsigned long long)(i - 1),
+                           (unsigned long long)i);
+        const Tid t = wm_of(i);
+        if (tid_gt_none(t) && (t.lsb & 1) == 0)
+            return c->fail(AD_E_INVAL, "ad_redundant_merge: entry %llu: redundantBefore watermark must be range-domain",
+                           (unsigned long long)i);
+    }
+    // One sweep over the pieces the two entry lists cut the key line into (a piece lies inside at most one entry of
+    // each list; boundaries compare alike under either inclusivity): the effective watermark -- the holding entry's,
+    // NONE without one -- may not fall back on any piece (CommandsForKey.java:1319, per piece); the pieces where it
+    // rose, touching ones of one watermark joined, are the risen spans the truncation examines.
+    struct Risen { int64_t start, end; uint64_t ent; };
+    std::vector<Risen> risen;
+    {
+        std::vector<int64_t> cuts;
+        cuts.reserve(2 * (n + n0));
+        for (uint64_t i = 0; i < n0; ++i) { cuts.push_back(B.start[i]); cuts.push_back(B.end[i]); }
+        for (uint64_t i = 0; i < n; ++i) { cuts.push_back(in->range_start[i]); cuts.push_back(in->range_end[i]); }
+        std::sort(cuts.begin(), cuts.end());
+        cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+        uint64_t io = 0, ii = 0;
+        for (size_t j = 0; j + 1 < cuts.size(); ++j)
+        {
+            const int64_t a = cuts[j], b = cuts[j + 1];
+            while (io < n0 && B.end[io] <= a) ++io;
+            while (ii < n && in->range_end[ii] <= a) ++ii;
+            const bool ho = io < n0 && B.start[io] <= a, hn = ii < n && in->range_start[ii] <= a;
+            const bool go = ho && tid_gt_none(B.wm[io]), gn = hn && tid_gt_none(wm_of(ii));
+            if (!go && !gn) continue;
+            const int cmp = !go ? 1 : !gn ? -1 : norm_cmp(norm(wm_of(ii)), norm(B.wm[io]));
+            if (cmp < 0 && !hn)
+                return c->fail(AD_E_INVAL, "ad_redundant_merge: the piece %s%lld, %lld%s of loaded entry %llu loses its coverage "
+                               "while its shardAppliedOrInvalidatedBefore is above NONE", incl ? "[" : "(", (long long)a,
+                               (long long)b, incl ? ")" : "]", (unsigned long long)io);
+            if (cmp < 0)
+                return c->fail(AD_E_INVAL, "ad_redundant_merge: entry %llu, piece %s%lld, %lld%s: expect the new "
+                               "shardAppliedOrInvalidatedBefore to be ahead of the existing one of loaded entry %llu "
+                               "(CommandsForKey.java:1319)", (unsigned long long)ii, incl ? "[" : "(", (long long)a, (long long)b,
+                               incl ? ")" : "]", (unsigned long long)io);
+            if (cmp == 0) continue;
+            if (!risen.empty() && risen.back().end == a && norm_cmp(norm(wm_of(risen.back().ent)), norm(wm_of(ii))) == 0)
+                risen.back().end = b;
+            else
+                risen.push_back({a, b, ii});
+        }
+    }
+    // the loaded boundaries: ad_redundant_advance (its checks passed above)
+    bool same = n == n0;
+    for (uint64_t i = 0; same && i < n; ++i) same = in->range_start[i] == B.start[i] && in->range_end[i] == B.end[i];
+    if (same)
+    {
+        c->n_trunc_examined = 0;
+        const int rc = ad_redundant_advance(c, in, stats);
+        if (!rc && stats) stats->n_probes = c->n_trunc_examined;      // the whole-store kernel: every key, if it ran
+        return rc;
+    }
+    if (stats) *stats = ad_stats{};
+    B.start.assign(in->range_start, in->range_start + n);
+    B.end.assign(in->range_end, in->range_end + n);
+    B.e0.assign(in->start_epoch, in->start_epoch + n);
+    B.e1.assign(in->end_epoch, in->end_epoch + n);
+    B.wm.resize(n);
+    for (uint64_t i = 0; i < n; ++i) B.wm[i] = wm_of(i);
+    c->rv_rng_gen = ~0ull;
+    // before the first build the snapshot reads them (and truncates) when it is built
+    if (!c->cfk.loaded || c->dirty) return AD_OK;
+    if (hipSetDevice(c->device) != hipSuccess) return c->fail(AD_E_DEVICE, "hipSetDevice");
+    StreamScope scope_(c->stream, c->cstream);
+    const double t0 = now_ms();
+    // the watermarks above NONE join the id dictionary; their member ranks (after a merge's remap, if one ran) are
+    // the new rb_wm -- every entry's, so the remapped ranks of the old entries need no reading back
+    std::vector<Tid> ids;
+    std::vector<uint64_t> at;
+    for (uint64_t i = 0; i < n; ++i)
+        if (tid_gt_none(B.wm[i]))
+        {
+            ids.push_back(B.wm[i]);
+            at.push_back(i);
+        }
+    std::vector<uint32_t> nr;
+    uint64_t n_new = 0;
+    if (int rc = dict_ensure_ids(c, ids, &nr, &n_new)) return rc;
+    std::vector<uint32_t> wr(n, 0);
+    for (size_t j = 0; j < at.size(); ++j) wr[at[j]] = nr[j];
+    if (int rc = upload(c, c->d_rb_wm, wr)) { c->dirty = true; return rc; }
+    const double ms_dict = now_ms() - t0;
+    // the entry ranges are part of the range table (range ids of the range commands, rb_rid, cells, KeyLines, trees)
+    const double t1 = now_ms();
+    uint64_t n_cmd_ids = 0;
+    if (int rc = refresh_range_part(c, c->cmds.txn.size(), &n_cmd_ids))
+    {
+        c->dirty = true;
+        return rc;
+    }
+    const double ms_refresh = now_ms() - t1;
+    std::vector<RbSpan> spans(risen.size());
+    for (size_t j = 0; j < risen.size(); ++j) spans[j] = RbSpan{risen[j].start, risen[j].end, wr[risen[j].ent], 0};
+    c->ms_truncate = 0;
+    c->n_truncated = 0;
+    c->n_trunc_keys = 0;
+    c->n_trunc_examined = 0;
+    if (int rc = truncate_to_rb(c, &spans)) return rc;
+    if (stats)
+    {
+        stats->ms_device = c->ms_truncate;
+        stats->ms_stage[0] = ms_dict;               // host-timed: watermark upload + dictionary growth
+        stats->ms_stage[1] = ms_refresh;            // host-timed: range part refresh
+        stats->n_keys[0] = c->n_truncated;
+        stats->n_keys[1] = c->n_trunc_keys;
+        stats->n_keys[2] = n_new;
+        stats->n_probes = c->n_trunc_examined;
     }
     return AD_OK;
 }

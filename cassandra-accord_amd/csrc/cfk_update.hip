@@ -32,6 +32,7 @@
 #include "devmem.hpp"
 #include "kernels.hpp"
 #include "levels.hpp"
+#include "wave.hpp"
 
 namespace adx {
 
@@ -2714,6 +2715,93 @@ __global__ void k_trunc_key(uint64_t nk, DevSnapshot s, KeyRec* krec, uint32_t* 
     if (chg) atomicAdd(n_chg, 1ull);
 }
 
+// byId segments from this length are searched by their wave (64 pivots a round, wave_lower_bound); shorter ones
+// by their own lane (at most 7 dependent loads). The wave takes its long keys one after the other, about two
+// dependent rounds each, so it pays only while they are few: above TRUNC_COOP_MAX long keys in a wave every lane
+// searches its own segment (log2 of the longest, in parallel). Both constants are reasoned, not measured.
+constexpr uint32_t TRUNC_COOP_MIN = 128;
+constexpr uint32_t TRUNC_COOP_MAX = 4;
+
+// k_trunc_key for the keys inside the risen spans only (ad_redundant_merge). The key array is ascending (ingest
+// checks it, new keys are merged in place), so a span holds one run of key ordinals [k0, k1): blockIdx.y walks the
+// spans, the blocks of a row stride over the span's run, lane per key. Every block of a row finds the run with
+// the same two searches (uniform loads, 2 * log2(nk) steps) -- no bounds pass and no read-back in between.
+// Sized for what a RedundantBefore.create step yields, one to a few spans (one per sub-range, more only when the
+// addition crosses entries of other watermarks): the repeated searches and the up to 64 blocks a row are noise
+// then. Thousands of tiny spans would still be correct (rows stride from 1024 spans on) but would want a bounds
+// pass and one flat grid instead.
+// t_pos / t_wm were cleared: the keys outside the spans keep 0. *n_exam counts the keys inside.
+__global__ __launch_bounds__(256) void k_trunc_spans(uint64_t nk, DevSnapshot s, const RbSpan* spans, uint64_t n_spans,
+                                                     KeyRec* krec, uint32_t* t_pos, uint32_t* t_wm,
+                                                     unsigned long long* n_chg, unsigned long long* n_exam)
+{
+    const uint32_t lane = lane_id();
+    const bool incl = s.start_inclusive != 0;
+    for (uint64_t sp = blockIdx.y; sp < n_spans; sp += gridDim.y)
+    {
+        const RbSpan span = spans[sp];
+        // keys before bound b's side of a range: key < b (StartInclusive), key <= b (EndInclusive)
+        auto ordinal = [&](int64_t b) -> uint64_t {
+            uint64_t lo = 0, hi = nk;
+            while (lo < hi)
+            {
+                const uint64_t m = (lo + hi) >> 1;
+                const int64_t x = s.keys[m];
+                if (incl ? x < b : x <= b) lo = m + 1;
+                else hi = m;
+            }
+            return lo;
+        };
+        const uint64_t k0 = ordinal(span.start), k1 = ordinal(span.end);
+        const uint64_t cnt = k1 > k0 ? k1 - k0 : 0;
+        if (blockIdx.x == 0 && threadIdx.x == 0 && cnt) atomicAdd(n_exam, (unsigned long long)cnt);
+        // block-uniform trip count: every lane of a wave reaches the ballots below
+        for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < cnt; base += (uint64_t)gridDim.x * blockDim.x)
+        {
+            const uint64_t i = base + threadIdx.x;
+            const bool on = i < cnt;
+            const uint64_t k = k0 + (on ? i : 0);
+            const KeyRec kr = krec[k];
+            uint32_t lo = kr.seg_lo, hi = kr.seg_hi;
+            const bool lng = on && hi - lo >= TRUNC_COOP_MIN;
+            const uint32_t n_lng = (uint32_t)__popcll(ballot(lng));
+            const bool coop = lng && n_lng <= TRUNC_COOP_MAX;
+            if (on && !coop)
+                while (lo < hi)
+                {
+                    const uint32_t m = (lo + hi) >> 1;
+                    if ((s.ent[m].y & RANK_MASK) < span.wm) lo = m + 1;
+                    else hi = m;
+                }
+            // long segments, one at a time by the whole wave
+            uint64_t todo = ballot(coop);
+            while (todo)
+            {
+                const int src = __ffsll((unsigned long long)todo) - 1;
+                todo &= todo - 1;
+                const uint32_t a = (uint32_t)__shfl((int)lo, src, 64), b = (uint32_t)__shfl((int)hi, src, 64);
+                const uint32_t p = (uint32_t)wave_lower_bound(
+                    a, b, [&](uint64_t x) { return s.ent[x].y & RANK_MASK; }, [&](uint32_t r) { return r < span.wm; });
+                if ((int)lane == src) lo = p;
+            }
+            const uint32_t pos = lo - kr.seg_lo;
+            bool chg = on && pos != 0;
+            if (on && kr.pruned && span.wm >= kr.pruned)
+            {
+                krec[k].pruned = 0;
+                chg = true;
+            }
+            if (on)
+            {
+                t_pos[k] = pos;
+                t_wm[k] = span.wm;
+            }
+            const uint32_t nc = (uint32_t)__popcll(ballot(chg));
+            if (lane == 0 && nc) atomicAdd(n_chg, (unsigned long long)nc);
+        }
+    }
+}
+
 // thread per entry: below its key's shardRedundantBefore (a prefix of the key's byId)
 __global__ void k_trunc_mark(uint64_t ne, const uint32_t* ekey, const KeyRec* krec, const uint32_t* t_pos, uint32_t* rm)
 {
@@ -2780,11 +2868,11 @@ __global__ void k_id_ranks(DevSnapshot s, DictSample ds, uint64_t n, const uint6
 int run_cfk_truncate(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, CfkDerivedBufs* bufs,
                      int (*need)(void* ctx, uint64_t cand, uint64_t cwr, uint64_t w, CfkDerivedBufs* bufs), void* need_ctx,
                      const CfkGrow& grow, hipStream_t st, CfkTruncOut* out, std::string* err, CfkMiss* miss,
-                     uint32_t* h_pos)
+                     uint32_t* h_pos, const RbSpan* spans, uint64_t n_spans)
 {
     *out = CfkTruncOut{};
     const uint64_t ne = s.n_ent, nk = s.n_keys;
-    if (!nk || !s.n_rb) return AD_OK;
+    if (!nk || !s.n_rb || (spans && !n_spans)) return AD_OK;
     if (!w->h_ctl && hipHostMalloc((void**)&w->h_ctl, sizeof(UpdCtl)) != hipSuccess) { *err = "pinned ctl"; return AD_E_NOMEM; }
     for (auto& e : w->ev)
         if (!e) UCHK(timing_event(&e));
@@ -2797,7 +2885,17 @@ int run_cfk_truncate(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, CfkDerivedBu
     uint32_t* t_pos = w->tpos.as<uint32_t>();
     uint32_t* t_wm = w->twm.as<uint32_t>();
     unsigned long long* n_chg = reinterpret_cast<unsigned long long*>(&ctl->tot2[1]);
-    k_trunc_key<<<blocks(nk), 256, 0, st>>>(nk, s, d.krec, t_pos, t_wm, n_chg);
+    if (spans)
+    {
+        // the keys outside the spans keep t_pos = t_wm = 0; a row of blocks per span (rows and blocks stride)
+        UCHK(hipMemsetAsync(t_pos, 0, 4 * nk, st));
+        UCHK(hipMemsetAsync(t_wm, 0, 4 * nk, st));
+        const dim3 grid(std::min(blocks(nk), 64u), (unsigned)std::min<uint64_t>(n_spans, 1024));
+        k_trunc_spans<<<grid, 256, 0, st>>>(nk, s, spans, n_spans, d.krec, t_pos, t_wm, n_chg,
+                                            reinterpret_cast<unsigned long long*>(&ctl->tot3[0]));
+    }
+    else
+        k_trunc_key<<<blocks(nk), 256, 0, st>>>(nk, s, d.krec, t_pos, t_wm, n_chg);
     if (ne)
     {
         UALLOC(w->uflag, 4 * ne, false);        // rm
@@ -2811,6 +2909,7 @@ int run_cfk_truncate(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, CfkDerivedBu
     UCHK(d2h(w->h_ctl, ctl, sizeof(UpdCtl), st));
     UCHK(hipStreamSynchronize(st));
     const uint64_t R = ne ? w->h_ctl->tot2[0] : 0, changed = w->h_ctl->tot2[1];
+    out->n_examined = spans ? w->h_ctl->tot3[0] : nk;
     auto finish = [&]() -> int {
         UCHK(hipEventRecord(w->ev[1], st));
         UCHK(hipEventSynchronize(w->ev[1]));

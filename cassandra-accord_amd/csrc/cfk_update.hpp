@@ -185,7 +185,15 @@ int run_cfk_prune(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const uint32_t*
 struct CfkTruncOut {
     uint64_t n_removed = 0;        // entries removed
     uint64_t n_keys = 0;           // CommandsForKeys that changed (entries left or prunedBefore cleared)
+    uint64_t n_examined = 0;       // keys whose byId was searched (every key, or the keys inside the spans)
     double ms_total = 0;
+};
+
+// A risen span of ad_redundant_merge: a stretch of the key line (a range in the store's inclusivity, inside one
+// RedundantBefore entry) whose shardRedundantBefore moved up to the dictionary rank wm (never 0)
+struct RbSpan {
+    int64_t start, end;
+    uint32_t wm, pad;
 };
 
 // CommandsForKey.withRedundantBeforeAtLeast (CommandsForKey.java:1317-1341) of every key to the
@@ -193,11 +201,13 @@ struct CfkTruncOut {
 // the key's shardRedundantBefore leave (compacted into the spare buffers), a prunedBefore at or below
 // it is cleared, the derived arrays are rebuilt, and with miss on the kept entries' missing() lists
 // lose the ids below it (Utils.removeRedundantMissing). h_pos (host, n_keys; may be null): each key's
-// count of removed entries, for host-held lists.
+// count of removed entries, for host-held lists. spans (device, n_spans ascending disjoint; null: every key):
+// only the keys inside them are examined, each against its span's watermark -- the other keys keep theirs
+// (ad_redundant_merge: the keys whose watermark did not move were truncated to it before).
 int run_cfk_truncate(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, CfkDerivedBufs* bufs,
                      int (*need)(void* ctx, uint64_t cand, uint64_t cwr, uint64_t w, CfkDerivedBufs* bufs), void* need_ctx,
                      const CfkGrow& grow, hipStream_t st, CfkTruncOut* out, std::string* err, CfkMiss* miss,
-                     uint32_t* h_pos);
+                     uint32_t* h_pos, const RbSpan* spans = nullptr, uint64_t n_spans = 0);
 
 // The ids (device arrays, n) join the dictionary where it does not hold them (appended, or merged
 // with the rank remap of an update batch: out->merged / merge_pos as run_cfk_update reports them);

@@ -336,6 +336,35 @@ int ad_redundant_load(ad_ctx* ctx, const ad_redundant_soa* rb);
  * ms_device = device time of the truncation, ms_stage[0] = the watermarks' dictionary growth (host-timed), n_keys[0]
  * = entries removed, n_keys[1] = CommandsForKeys changed, n_keys[2] = ids added to the dictionary. */
 int ad_redundant_advance(ad_ctx* ctx, const ad_redundant_soa* rb, ad_stats* stats);
+/* ad_redundant_merge: as ad_redundant_advance, but the entry boundaries may change -- what each GC or bootstrap
+ * step does when it folds a RedundantBefore.create(ranges, ...) for part of a shard into the map
+ * (RedundantBefore.merge, RedundantBefore.java:375-377, from CommandStore.java:314,513,524,551): entries are split
+ * where the new ranges cut them (Builder.slice, :473-479) and touching entries that became equal are joined
+ * (tryMergeEqual, :488-498). rb is the store's WHOLE RedundantBefore AFTER the merge, as the host computed it
+ * (ascending, disjoint, as for ad_redundant_load; count and boundaries free). The library does not merge or
+ * coalesce: equalsIgnoreRange compares fields it does not hold (locallyAppliedOrInvalidatedBefore, bootstrappedAt,
+ * staleUntilAtLeast), and a join Java did not make would change the range keys collectDeps emits.
+ *
+ * Accepted iff the effective watermark -- the holding entry's shardAppliedOrInvalidatedBefore, NONE where no entry
+ * holds the point -- at every point of the key line is at or above the loaded one: the precondition of
+ * CommandsForKey.withRedundantBeforeAtLeast (CommandsForKey.java:1319) per piece of the two entry lists' common
+ * refinement, in the store's inclusivity (ad_config.range_start_inclusive). AD_E_INVAL, with the store untouched and
+ * the entry or piece named in ad_last_error, for: a piece whose watermark falls back; a piece that loses its
+ * coverage while its loaded watermark was above NONE; entries that are unsorted, overlapping or empty; a
+ * key-domain watermark; null arrays with n > 0.
+ *
+ * Before the first build (nothing loaded, or a load pending) the host copy is replaced and the next build reads it.
+ * On a built snapshot, without a rebuild: the watermarks join the id dictionary on the device; the entry arrays are
+ * replaced; the range part (range table -- it holds the entry ranges, so range ids shift --, rb range ids, stabbing
+ * cells, KeyLines, range trees) is refreshed as ad_range_cmds_update does, also from or to an empty map; and the
+ * CommandsForKeys of the risen spans -- the maximal stretches of the key line whose effective watermark rose -- are
+ * truncated on the device exactly as ad_redundant_advance truncates (missing() lists wherever they are held,
+ * prunedBefore, derived arrays). Keys whose watermark did not move are not examined: they were truncated to it
+ * before (ad_cfk_update leaves the filter below it to the caller, above). With exactly the loaded boundaries the
+ * call IS ad_redundant_advance. stats (may be NULL) as ad_redundant_advance, and: ms_stage[1] = the range part
+ * refresh (host-timed; 0 when the boundaries did not change), n_probes = keys examined by the truncation (the keys
+ * inside the risen spans; every key on the ad_redundant_advance route). */
+int ad_redundant_merge(ad_ctx* ctx, const ad_redundant_soa* rb, ad_stats* stats);
 /* Build the id dictionary and device indexes of the loaded snapshot now (otherwise the first
  * batch does it). Ingest time is reported in ad_stats.ms_ingest, never in ms_device. */
 int ad_prepare(ad_ctx* ctx);
