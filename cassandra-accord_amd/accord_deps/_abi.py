@@ -175,6 +175,12 @@ class AdMerged(C.Structure):
                 ("ms_device", C.c_double), ("id_format", C.c_uint32)]
 
 
+class AdScopeSoa(C.Structure):
+    """ad_scope_soa (ad_deps_intersect): destination range lists (host), routes and domain bytes (device)."""
+    _fields_ = [("n_dest", C.c_uint32), ("dest_off", P), ("dest_start", P), ("dest_end", P),
+                ("domain", P), ("route_off", P), ("route", P)]
+
+
 class AdExchangeStats(C.Structure):
     _fields_ = [("bytes_moved", C.c_uint64), ("ms_export", C.c_double), ("ms_move", C.c_double),
                 ("ms_merge", C.c_double), ("ms_total", C.c_double)]

@@ -605,3 +605,155 @@ class Workload:
             en.append(r[:, 1])
         cat = (lambda xs: np.ascontiguousarray(np.concatenate(xs) if xs else np.zeros(0, np.int64), np.int64))
         return off, cat(st), cat(en)
+
+
+@dataclass
+class Routes:
+    """One route per owned request (ad_scope_soa): request r's words are words[off[r]:off[r + 1]] -- ascending key
+    ordinals (domain[r] == 0: a key route), or ascending disjoint ranges as {start, end} pairs (domain[r] == 1)."""
+    domain: np.ndarray          # u8 [n]
+    off: np.ndarray             # u64 [n + 1], in words
+    words: np.ndarray           # i64
+
+    def __post_init__(self):
+        self.domain = A.as_u8(self.domain)
+        self.off = A.as_u64(self.off)
+        self.words = A.as_i64(self.words)
+
+    def __len__(self):
+        return len(self.domain)
+
+    def of(self, r):
+        """(is_range_route, [key, ..] or [(start, end), ..]) of request r."""
+        w = self.words[int(self.off[r]):int(self.off[r + 1])].tolist()
+        if self.domain[r]:
+            return True, list(zip(w[0::2], w[1::2]))
+        return False, w
+
+    @staticmethod
+    def from_lists(routes):
+        """routes: per request (is_range_route, [key, ..] or [(start, end), ..])."""
+        dom, off, words = [], [0], []
+        for is_range, items in routes:
+            dom.append(1 if is_range else 0)
+            for it in items:
+                words.extend(it if is_range else (it,))
+            off.append(len(words))
+        return Routes(np.array(dom, np.uint8), np.array(off, np.uint64), np.array(words, np.int64))
+
+
+def range_contains(s, e, k, start_inclusive):
+    """Range.contains(key) (Range.java:287-290) for Range.StartInclusive [s, e) / Range.EndInclusive (s, e]."""
+    return s <= k < e if start_inclusive else s < k <= e
+
+
+def ranges_intersect(a, b):
+    """Range.compareIntersecting(that) == 0 (Range.java:296-305): the bounds alone decide."""
+    return not (a[0] >= b[1] or a[1] <= b[0])
+
+
+def route_slice(route, ranges, start_inclusive):
+    """route.slice(ranges) (Deps.java:205-218 callers: Accept.java:71, Commit.java:144, Apply.java:81). A key route
+    keeps the keys some range contains (AbstractKeys.slice, AbstractKeys.java:183-186: Range.compareTo); a range
+    route becomes the intersections of its ranges with `ranges` (AbstractRanges.sliceMinimal, AbstractRanges.java:
+    329-374: every intersecting pair gives max of the starts, min of the ends)."""
+    is_range, items = route
+    if not is_range:
+        return False, [k for k in items if any(range_contains(s, e, k, start_inclusive) for s, e in ranges)]
+    out = []
+    for a in items:
+        for b in ranges:
+            if ranges_intersect(a, b):
+                out.append((max(a[0], b[0]), min(a[1], b[1])))
+    return True, out
+
+
+def _trim_unused_values(n_keys, ids, k2t):
+    """RelationMultiMap.trimUnusedValues (RelationMultiMap.java:491-532): a bitmap of the ids the lists still name
+    (:502-503), each kept id's new index in order (:506-510), the ids compacted (:516-520) and the lists remapped
+    (:522-523). ids: index list into the input's ids."""
+    used = [False] * len(ids)
+    for v in k2t[n_keys:]:
+        used[v] = True
+    remap, kept = [-1] * len(ids), []
+    for i, u in enumerate(used):
+        if u:
+            remap[i] = len(kept)
+            kept.append(ids[i])
+    if len(kept) < len(ids):
+        k2t = k2t[:n_keys] + [remap[v] for v in k2t[n_keys:]]
+    return kept, k2t
+
+
+def _select(n_keys, n_ids, k2t, sel):
+    """KeyDeps.select (KeyDeps.java:206-248) / RangeDeps.build over the collector's ranges (RangeDeps.java:623-635,
+    RangeAndMapCollector :868-917): nothing selected -> the empty map (:209-210, :625-626); everything -> `this`
+    (:212-213, :628-629); else the selected keys' end offsets (from the number selected on) and lists, then
+    trimUnusedValues. sel: ascending indices of the selected keys. Returns (key indices, id indices, k2t)."""
+    if not sel:
+        return [], [], []
+    if len(sel) == n_keys:
+        return list(range(n_keys)), list(range(n_ids)), list(k2t)
+    heads, lists = [], []
+    for i in sel:
+        start = n_keys if i == 0 else k2t[i - 1]
+        lists.extend(k2t[start:k2t[i]])
+        heads.append(len(sel) + len(lists))
+    ids, out = _trim_unused_values(len(sel), list(range(n_ids)), heads + lists)
+    return list(sel), ids, out
+
+
+def deps_intersecting(batch, routes, dest_ranges, start_inclusive):
+    """deps.intersecting(route(r).slice(R_d)) (Deps.java:215-218) of every request r of `batch` (a
+    PartialDepsBatch: the coordinator's merged deps) and every destination d, as a PartialDepsBatch whose row
+    d * n + r is that PartialDeps. The CPU restatement ad_deps_intersect is tested against: plain loops over the
+    Java's steps.
+      keyDeps, directKeyDeps  KeyDeps.intersecting / slice (KeyDeps.java:189-204): keys.intersecting(scope) --
+        the map's keys equal to a scope key (Keys.java:111-119) or contained in a scope range
+        (AbstractKeys.java:212-215) --, then select;
+      rangeDeps  RangeDeps.intersecting (RangeDeps.java:584-621): per scope key / range in order, forEach visits
+        the map's ranges that contain it / intersect it, from minIndex on (RangeDeps.java:223-235); what one scope
+        item visits out of order is sorted by the collector before it is copied (RangeCollector.accept, :816-831)
+        and precedes the item's in-order run, and the next item starts after that run (CheckpointIntervalArray.java:
+        162-249 returns `end`): the ranges come out in input order, each once, whole (copy, :833-842). The map's
+        ranges are sorted by start then end (Range.compare), so "visited by some scope item" is all that decides."""
+    n = batch.n_txns
+    if len(routes) != n:
+        raise ValueError("one route per request")
+    dests = [[(int(s), int(e)) for s, e in np.asarray(r, np.int64).reshape(-1, 2)] for r in dest_ranges]
+    cols = [dict(ko=[0], keys=[], ends=[], to=[0], ids=[], oo=[0], k2t=[]) for _ in range(A.NMAPS)]
+    for d in range(len(dests)):
+        for r in range(n):
+            is_range, scope = route_slice(routes.of(r), dests[d], start_inclusive)
+            for m in range(A.NMAPS):
+                ks, ke, t, k2t = batch.maps[m].request(r)
+                ks, k2t = ks.tolist(), k2t.tolist()
+                ke = None if ke is None else ke.tolist()
+                sel = []
+                for i in range(len(ks)):
+                    if m != A.AD_MAP_RANGE:
+                        hit = (any(range_contains(s, e, ks[i], start_inclusive) for s, e in scope) if is_range
+                               else ks[i] in scope)
+                    elif is_range:
+                        hit = any(ranges_intersect((ks[i], ke[i]), x) for x in scope)
+                    else:
+                        hit = any(range_contains(ks[i], ke[i], k, start_inclusive) for k in scope)
+                    if hit:
+                        sel.append(i)
+                ki, ii, ok2t = _select(len(ks), len(t), k2t, sel)
+                c = cols[m]
+                c["keys"] += [ks[i] for i in ki]
+                if ke is not None:
+                    c["ends"] += [ke[i] for i in ki]
+                c["ids"].append(t.take(np.asarray(ii, np.int64)))
+                c["k2t"] += ok2t
+                c["ko"].append(len(c["keys"]))
+                c["to"].append(c["to"][-1] + len(ii))
+                c["oo"].append(len(c["k2t"]))
+    maps = []
+    for m, c in enumerate(cols):
+        ids = Tids.concat(c["ids"]) if c["ids"] else Tids(np.zeros(0, np.uint64), np.zeros(0, np.uint64), np.zeros(0, np.int32))
+        maps.append(DepsMap(np.array(c["ko"], np.uint64), np.array(c["keys"], np.int64),
+                            np.array(c["ends"], np.int64) if m == A.AD_MAP_RANGE else None,
+                            np.array(c["to"], np.uint64), ids, np.array(c["oo"], np.uint64), np.array(c["k2t"], np.int32)))
+    return PartialDepsBatch(maps)

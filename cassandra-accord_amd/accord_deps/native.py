@@ -30,7 +30,8 @@ EXPORTS = ("ad_abi_version", "ad_ctx_create", "ad_ctx_destroy", "ad_last_error",
            "ad_check_result_device", "ad_check_snapshot", "ad_cfk_prune", "ad_cfk_byid", "ad_cfk_missing",
            "ad_cfk_load_pruned", "ad_host_register", "ad_host_unregister", "ad_deps_batch_into",
            "ad_debug_guard_check", "ad_host_alloc", "ad_host_free", "ad_cfk_update_status",
-           "ad_slice_sets_load", "ad_redundant_advance", "ad_range_cmds_update", "ad_redundant_merge")
+           "ad_slice_sets_load", "ad_redundant_advance", "ad_range_cmds_update", "ad_redundant_merge",
+           "ad_deps_intersect")
 
 
 class AccordDepsError(RuntimeError):
@@ -79,6 +80,8 @@ def lib():
         L.ad_copy_to_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         L.ad_parts_union.argtypes = [C.c_void_p, C.POINTER(A.AdParts), C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64,
                                      C.c_void_p, C.POINTER(A.AdMerged)]
+        L.ad_deps_intersect.argtypes = [C.c_void_p, C.POINTER(A.AdMerged), C.POINTER(A.AdScopeSoa), C.c_void_p,
+                                        C.POINTER(A.AdMerged)]
         L.ad_set_global_dict.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ad_preaccept_maps_load.argtypes = [C.c_void_p, C.POINTER(A.AdRangeMapSoa), C.POINTER(A.AdRangeMapSoa)]
         L.ad_preaccept_device.argtypes = [C.c_void_p, C.POINTER(A.AdQuerySoa), C.c_uint32, C.c_uint64, C.c_void_p,
@@ -671,6 +674,36 @@ class DeviceCommandStore:
         out = A.AdMerged()
         self._check(lib().ad_parts_union(self.h, C.byref(parts), len(sp), A.ptr(sp), txn_base, n_owned, stream,
                                          C.byref(out)))
+        return out
+
+    def intersect_merged(self, mg, dest_ranges, routes, stream=None):
+        """ad_deps_intersect: Deps.intersecting(route.slice(R_d)) of every owned request of the AdMerged `mg` for
+        every destination d. dest_ranges: per destination an (k, 2) array of sorted, disjoint ranges (k may be 0);
+        routes: a model.Routes (one route per owned request; staged in HBM here) or a (domain, route_off, route)
+        triple of device pointers. Returns an AdMerged (device) whose row d * mg.n_txns + r is request r's part for
+        destination d; merged_to_host reads it."""
+        import torch
+        sc = A.AdScopeSoa()
+        rs = [np.asarray(r, np.int64).reshape(-1, 2) for r in dest_ranges]
+        off = np.zeros(len(rs) + 1, np.uint64)
+        off[1:] = np.cumsum([len(r) for r in rs])
+        cat = np.concatenate(rs) if rs else np.zeros((0, 2), np.int64)
+        ds, de = np.ascontiguousarray(cat[:, 0]), np.ascontiguousarray(cat[:, 1])
+        sc.n_dest, sc.dest_off, sc.dest_start, sc.dest_end = len(rs), A.ptr(off), A.ptr(ds), A.ptr(de)
+        keep = None
+        if isinstance(routes, tuple):
+            sc.domain, sc.route_off, sc.route = routes
+        else:
+            dev = torch.device("cuda", self.device)
+            # (one spare element each: an empty tensor has no address)
+            keep = [torch.from_numpy(np.append(np.asarray(routes.domain, np.uint8), np.uint8(0))).to(dev),
+                    torch.from_numpy(np.append(np.asarray(routes.off, np.uint64), np.uint64(0)).view(np.int64)).to(dev),
+                    torch.from_numpy(np.append(np.asarray(routes.words, np.int64), np.int64(0))).to(dev)]
+            torch.cuda.synchronize(dev)
+            sc.domain, sc.route_off, sc.route = (t.data_ptr() for t in keep)
+        out = A.AdMerged()
+        self._check(lib().ad_deps_intersect(self.h, C.byref(mg), C.byref(sc), stream, C.byref(out)))
+        del keep
         return out
 
     def comm_init(self, uid, rank, world):

@@ -1406,3 +1406,52 @@ def with_epoch_slices(w, seed, store_every=0, n_epochs=3):
     q.min_epoch = np.array([rng.integers(1, max(1, e) + 1) for e in ex_ep], np.int64)
     from dataclasses import replace
     return with_slice_sets(replace(w, queries=q), rfe, store_every)
+
+
+def deps_scopes(w, n_dest, seed, two_ranges=True, empty_dest=True, drop_frac=0.15, range_route_frac=0.0):
+    """What ad_deps_intersect needs beside the merged deps of w's requests: (model.Routes, dest_ranges).
+    Routes: a key-domain request's route is its keys, each dropped with probability drop_frac (a route names
+    the keys of the transaction, its deps may name more) -- or, with probability range_route_frac, ranges drawn
+    around those keys; a range-domain request's route is its ranges. dest_ranges: a random split of the token
+    space into pieces dealt to the n_dest destinations (sorted, disjoint (k, 2) arrays): with two_ranges one
+    destination owns two pieces, with empty_dest (and n_dest >= 2) one owns none. The cuts fall on keys and range
+    bounds of the workload, so keys sit exactly on boundaries."""
+    from .model import Routes
+    rng = np.random.default_rng(seed)
+    q = w.queries
+    routes = []
+    for i in range(len(q)):
+        rr = q.ranges_of(i)
+        if rr:
+            routes.append((True, rr))
+            continue
+        keys = q.keys[int(q.key_off[i]):int(q.key_off[i + 1])]
+        keys = sorted(set(int(k) for k in keys if rng.random() >= drop_frac))
+        if keys and rng.random() < range_route_frac:
+            out = []
+            for k in keys:
+                s, e = k - int(rng.integers(0, 3)), k + int(rng.integers(0, 3))
+                if s == e:
+                    e += 1
+                if out and s < out[-1][1]:
+                    out[-1] = (out[-1][0], max(out[-1][1], e))
+                else:
+                    out.append((s, e))
+            routes.append((True, out))
+        else:
+            routes.append((False, keys))
+    lo, hi = -(1 << 63), (1 << 63) - 1
+    owners = n_dest - (1 if empty_dest and n_dest >= 2 else 0)
+    pieces = owners + (1 if two_ranges else 0)
+    cand = np.unique(np.concatenate([w.cfk.keys, w.cmds.range_start, w.cmds.range_end, q.keys]))
+    cand = cand[(cand > lo) & (cand < hi)]
+    n_cuts = min(pieces - 1, len(cand))
+    cuts = sorted(int(x) for x in rng.choice(cand, n_cuts, replace=False)) if n_cuts else []
+    bounds = [lo] + cuts + [hi]
+    segs = [(bounds[i], bounds[i + 1]) for i in range(len(bounds) - 1)]
+    order = [int(x) for x in rng.permutation(len(segs))]
+    dest = [[] for _ in range(n_dest)]
+    who = [int(x) for x in rng.permutation(n_dest)][:owners]
+    for j, si in enumerate(order):
+        dest[who[j % owners]].append(segs[si])
+    return Routes.from_lists(routes), [np.array(sorted(d), np.int64).reshape(-1, 2) for d in dest]

@@ -357,6 +357,139 @@ int ad_parts_union(ad_ctx* c, const ad_parts* in, uint32_t n_src, const uint64_t
     return parts_merge(c, in, n_src, src_parts, txn_base, n_owned, stream, out, true);
 }
 
+// Deps.intersecting(route.slice(R_d)) of every owned request for every destination (Deps.java:205-218; Accept.java:71,
+// Commit.java:144, Apply.java:81): size pass over the (destination, request, map) groups, the offset scan -- which
+// is the result's CSR --, one read-back of the totals to size the result, emit pass (intersect.hip).
+int ad_deps_intersect(ad_ctx* c, const ad_merged* in, const ad_scope_soa* sc, void* stream, ad_merged* out)
+{
+    if (!c || !in || !sc || !out) return AD_E_INVAL;
+    if (in->id_format != AD_IDS_TRIPLET && in->id_format != AD_IDS_RANK)
+        return c->fail(AD_E_INVAL, "ad_deps_intersect: unknown id_format %u", in->id_format);
+    const uint64_t n_owned = in->n_txns;
+    const uint32_t n_dest = sc->n_dest;
+    if (n_dest == 0 || !sc->dest_off) return c->fail(AD_E_INVAL, "ad_deps_intersect: n_dest and dest_off are required");
+    if (sc->dest_off[0] != 0) return c->fail(AD_E_INVAL, "ad_deps_intersect: dest_off must start at 0");
+    for (uint32_t d = 0; d < n_dest; ++d)
+        if (sc->dest_off[d] > sc->dest_off[d + 1]) return c->fail(AD_E_INVAL, "ad_deps_intersect: dest_off not ascending");
+    const uint64_t n_dr = sc->dest_off[n_dest];
+    if (n_dr && (!sc->dest_start || !sc->dest_end)) return c->fail(AD_E_INVAL, "ad_deps_intersect: destination ranges are NULL");
+    for (uint32_t d = 0; d < n_dest; ++d)
+        for (uint64_t i = sc->dest_off[d]; i < sc->dest_off[d + 1]; ++i)
+        {
+            if (sc->dest_start[i] >= sc->dest_end[i])
+                return c->fail(AD_E_INVAL, "ad_deps_intersect: empty range %llu of destination %u", (unsigned long long)i, d);
+            if (i > sc->dest_off[d] && sc->dest_end[i - 1] > sc->dest_start[i])
+                return c->fail(AD_E_INVAL, "ad_deps_intersect: ranges of destination %u unsorted or overlapping at %llu", d,
+                               (unsigned long long)i);
+        }
+    if (n_owned)
+    {
+        if (!sc->route_off || !sc->route) return c->fail(AD_E_INVAL, "ad_deps_intersect: route arrays are NULL");
+        for (int m = 0; m < 3; ++m)
+            if (!in->keys_off[m] || !in->txn_off[m] || !in->k2t_off[m] || (in->n_keys[m] && !in->keys[m]) ||
+                (in->n_ids[m] && !in->txns[m]) || (in->n_k2t[m] && !in->k2t[m]))
+                return c->fail(AD_E_INVAL, "ad_deps_intersect: input map %d has NULL arrays", m);
+    }
+    const uint64_t N = (uint64_t)n_dest * n_owned;
+    if (3 * N >= (1ull << 31)) return c->fail(AD_E_CAPACITY, "ad_deps_intersect: %llu result rows", (unsigned long long)N);
+    if (hipSetDevice(c->device) != hipSuccess) return c->fail(AD_E_DEVICE, "hipSetDevice");
+    StreamScope scope_(c->stream, c->cstream);
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    scope_.add(st);
+    // destination ranges: {dest_off [n_dest + 1], start [n_dr], end [n_dr]} in one buffer
+    std::vector<uint64_t> dw(n_dest + 1 + 2 * n_dr);
+    memcpy(dw.data(), sc->dest_off, sizeof(uint64_t) * (n_dest + 1));
+    if (n_dr)
+    {
+        memcpy(dw.data() + n_dest + 1, sc->dest_start, sizeof(int64_t) * n_dr);
+        memcpy(dw.data() + n_dest + 1 + n_dr, sc->dest_end, sizeof(int64_t) * n_dr);
+    }
+    if (!ens<uint64_t>(c->i_dest, dw.size()) || !ens<uint32_t>(c->i_gsz, 9 * N) || !ens<uint64_t>(c->i_goff, 9 * (N + 1)) ||
+        !ens<uint64_t>(c->i_bsum, 9 * ((N + 1023) / 1024) + 16) || !ens<uint32_t>(c->i_heavy, 3 * N) ||
+        !ens<uint64_t>(c->i_ctl, 16))
+        return c->fail(AD_E_NOMEM, "intersect buffers");
+    IntersectArgs a{};
+    a.n_owned = n_owned;
+    a.n_dest = n_dest;
+    a.rank_ids = in->id_format == AD_IDS_RANK;
+    a.start_inclusive = c->cfg.range_start_inclusive != 0;
+    for (int m = 0; m < 3; ++m)
+    {
+        a.keys_off[m] = in->keys_off[m]; a.keys[m] = in->keys[m];
+        a.txn_off[m] = in->txn_off[m]; a.txns[m] = in->txns[m];
+        a.k2t_off[m] = in->k2t_off[m]; a.k2t[m] = in->k2t[m];
+    }
+    a.dest_off = c->i_dest.as<uint64_t>();
+    a.dest_start = c->i_dest.as<int64_t>() + n_dest + 1;
+    a.dest_end = a.dest_start + n_dr;
+    a.domain = sc->domain;
+    a.route_off = sc->route_off;
+    a.route = sc->route;
+    a.gsz = c->i_gsz.as<uint32_t>();
+    a.goff = c->i_goff.as<uint64_t>();
+    a.heavy = c->i_heavy.as<uint32_t>();
+    // control words: [0] error bits, [1] heavy groups, [2, 13) what k_isect_totals gathers
+    a.error = c->i_ctl.as<uint32_t>();
+    a.n_heavy = c->i_ctl.as<uint32_t>() + 2;
+    uint64_t* d_tot = c->i_ctl.as<uint64_t>() + 2;
+    HIPCHK(c, hipEventRecord(c->ev[6], st));
+    HIPCHK(c, h2d(c->i_dest.p, dw.data(), sizeof(uint64_t) * dw.size(), st));
+    HIPCHK(c, hipMemsetAsync(c->i_ctl.p, 0, sizeof(uint64_t) * 16, st));
+    HIPCHK(c, run_intersect_size(a, st));
+    HIPCHK(c, run_scan_arrays(a.gsz, c->i_goff.as<uint64_t>(), N, 9, c->i_bsum.as<uint64_t>(), st));
+    HIPCHK(c, run_intersect_totals(a, d_tot, st));
+    uint64_t* rb = rb_slot(c);
+    if (!rb) return c->fail(AD_E_NOMEM, "pinned read-back words");
+    HIPCHK(c, hipMemcpyAsync(rb, d_tot, sizeof(uint64_t) * 11, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    uint64_t tot[11];
+    memcpy(tot, rb, sizeof(tot));
+    if (tot[9] & IS_E_ROUTE) return c->fail(AD_E_INVAL, "ad_deps_intersect: route_off must start at 0 and ascend");
+    if (tot[9] & IS_E_INPUT) return c->fail(AD_E_INVAL, "ad_deps_intersect: malformed keysToTxnIds in the input");
+    if (tot[9] & IS_E_IDS) return c->fail(AD_E_CAPACITY, "ad_deps_intersect: a map of more than %u ids", IS_MAX_IDS);
+    // tot[3 k + m]: keys (ranges), ids, keysToTxnIds ints of map m over all rows; the maps follow each other in
+    // one array per kind
+    uint64_t kb[4] = {0, 0, 0, 0}, ib[4] = {0, 0, 0, 0}, tb[4] = {0, 0, 0, 0};
+    for (int m = 0; m < 3; ++m)
+    {
+        kb[m + 1] = kb[m] + tot[m] * (m == AD_MAP_RANGE ? 2 : 1);
+        ib[m + 1] = ib[m] + tot[3 + m];
+        tb[m + 1] = tb[m] + tot[6 + m];
+    }
+    if (!ens<int64_t>(c->i_keys, kb[3]) || !ens<int64_t>(c->i_ids, a.rank_ids ? (ib[3] + 1) / 2 : 3 * ib[3]) ||
+        !ens<int32_t>(c->i_k2t, tb[3]))
+        return c->fail(AD_E_NOMEM, "intersect outputs");
+    for (int m = 0; m < 3; ++m)
+    {
+        a.o_keys[m] = c->i_keys.as<int64_t>() + kb[m];
+        a.o_ids[m] = a.rank_ids ? (void*)(c->i_ids.as<uint32_t>() + ib[m]) : (void*)(c->i_ids.as<int64_t>() + 3 * ib[m]);
+        a.o_k2t[m] = c->i_k2t.as<int32_t>() + tb[m];
+    }
+    HIPCHK(c, run_intersect_emit(a, (uint32_t)tot[10], st));
+    HIPCHK(c, hipEventRecord(c->ev[7], st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev[6], c->ev[7]));
+    memset(out, 0, sizeof(*out));
+    out->n_txns = N;
+    out->txn_base = in->txn_base;
+    out->ms_device = ms;
+    out->id_format = in->id_format;
+    for (int m = 0; m < 3; ++m)
+    {
+        out->keys_off[m] = c->i_goff.as<uint64_t>() + (uint64_t)(0 + m) * (N + 1);
+        out->txn_off[m] = c->i_goff.as<uint64_t>() + (uint64_t)(3 + m) * (N + 1);
+        out->k2t_off[m] = c->i_goff.as<uint64_t>() + (uint64_t)(6 + m) * (N + 1);
+        out->keys[m] = a.o_keys[m];
+        out->txns[m] = (int64_t*)a.o_ids[m];
+        out->k2t[m] = a.o_k2t[m];
+        out->n_keys[m] = tot[m];
+        out->n_ids[m] = tot[3 + m];
+        out->n_k2t[m] = tot[6 + m];
+    }
+    return AD_OK;
+}
+
 // =======================================================================================
 // Node exchange (SURVEY §8 e): the per-store PartialDeps of a node batch combined
 // on the store that owns each request -- CommandStores.mapReduce's reduce (CommandStores.java:576-593)

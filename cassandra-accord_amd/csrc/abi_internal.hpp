@@ -29,6 +29,7 @@
 #include "../../include/accord_deps.h"
 #include "common.hpp"
 #include "exchange.hpp"
+#include "intersect.hpp"
 #include "kernels.hpp"
 #include "levels.hpp"
 #include "cfk_update.hpp"
@@ -279,6 +280,8 @@ struct ad_ctx {
     DevBuf m_src, m_psz, m_poff, m_slot, m_dup, m_gsz, m_goff, m_bsum, m_err, m_bases;
     DevBuf m_ko, m_to, m_oo, m_keys, m_ids, m_k2t, m_u, m_ppre;
     DevBuf m_kdp, m_kuk, m_khead, m_pdp, m_ppos;   // ad_parts_union scratch
+    // ad_deps_intersect: destination ranges, group sizes / offsets (the result's CSR), heavy list, control words, result
+    DevBuf i_dest, i_gsz, i_goff, i_bsum, i_heavy, i_ctl, i_keys, i_ids, i_k2t;
     // maxConflicts / rejectBefore of the PreAccept timestamp proposal (ad_preaccept_maps_load)
     struct RangeMapBufs {
         DevBuf starts, msb, lsb, node, present;

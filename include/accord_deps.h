@@ -516,6 +516,48 @@ int ad_parts_merge(ad_ctx* ctx, const ad_parts* in_dev, uint32_t n_src, const ui
 int ad_parts_union(ad_ctx* ctx, const ad_parts* in_dev, uint32_t n_src, const uint64_t* src_parts,
                    uint64_t txn_base, uint64_t n_owned, void* stream, ad_merged* out);
 
+/* ---- Deps.intersecting: each replica's part of the merged deps -------------------------------
+ * The coordinator never sends its Deps whole: every Accept, Commit and Apply to a replica carries
+ * deps.intersecting(scope), scope = route.slice(rangesForNode(to)) (Accept.java:71, Commit.java:144,
+ * Apply.java:81; Deps.intersecting Deps.java:215-218, Deps.slice :205-208). ad_deps_intersect does that for
+ * every owned request of an ad_merged (ad_parts_union / ad_parts_merge, either id_format) and every
+ * destination at once.
+ *
+ * Destinations: n_dest sorted, disjoint range lists R_d (host arrays, the ctx's inclusivity,
+ * ad_config.range_start_inclusive); a list may be empty. Routes: per owned request r the words
+ * route[route_off[r] .. route_off[r + 1]) (device arrays; route_off[0] == 0): ascending key ordinals
+ * (domain[r] == 0), or ascending disjoint ranges as {start, end} pairs (domain[r] == 1). scope(r, d) =
+ * route(r).slice(R_d): the route keys inside R_d, or the intersections of the route ranges with R_d. */
+typedef struct ad_scope_soa {
+    uint32_t        n_dest;
+    const uint64_t* dest_off;     /* host [n_dest + 1], dest_off[0] == 0: ranges of destination d       */
+    const int64_t*  dest_start;   /* host [dest_off[n_dest]]                                            */
+    const int64_t*  dest_end;
+    const uint8_t*  domain;       /* device [n_txns] 0: key route, 1: range route; NULL: all key routes */
+    const uint64_t* route_off;    /* device [n_txns + 1], in words of `route`                           */
+    const int64_t*  route;        /* device                                                             */
+} ad_scope_soa;
+
+/* Row d * in->n_txns + r of *out (n_txns = n_dest * in->n_txns, txn_base and id_format as in `in`) holds, per
+ * map, what the reference computes for request r and destination d:
+ *   keyDeps, directKeyDeps: the map's keys in scope(r, d) -- equal to a scope key, or inside a scope range
+ *     (KeyDeps.intersecting / slice, then select; KeyDeps.java:189-248);
+ *   rangeDeps: in input order and each once, the map's ranges that hold a scope key
+ *     (RangeDeps.intersecting, RangeDeps.java:611-621) or intersect a scope range (slice, :594-609;
+ *     Range.compareIntersecting, Range.java:296-305), whole, not trimmed (RangeCollector.copy, :833-842) --
+ *     so a range inside R_d that holds no route key is dropped under a key route and kept under a range route;
+ *   every map: RelationMultiMap.trimUnusedValues (:491-532) -- txnIds the ascending subsequence of the
+ *     input's ids some selected key still names, keysToTxnIds the selected keys' end offsets and lists with
+ *     the id indices remapped. Nothing selected: an empty map; everything selected: the input's arrays.
+ * (An input map with ids but no ranges would keep its ids in Java, RangeDeps.java:601-602; the builders and
+ * unions that produce an ad_merged never make one, so an empty input map gives an empty map here.)
+ * Device memory owned by ctx, valid until the next ad_deps_intersect on ctx; it never aliases `in`, which
+ * stays valid and unchanged. Needs no snapshot. All work is enqueued on `stream` (NULL: the ctx stream) and
+ * complete on return. AD_E_INVAL, with nothing changed: a NULL argument or array, destination ranges empty,
+ * unsorted or overlapping, a route CSR that does not start at 0 or descends, malformed input maps;
+ * AD_E_CAPACITY: a map of more than 131072 ids, or 2^31 / 3 result rows and more. */
+int ad_deps_intersect(ad_ctx* ctx, const ad_merged* in, const ad_scope_soa* scope, void* stream, ad_merged* out);
+
 /* ---- node exchange (SURVEY §8 e): combine the stores' PartialDeps on the owning store --------
  * After every store of a node resolved its share of a node batch (ad_deps_batch_device, AD_PARTS_ONLY
  * is enough), each store's parts are exported grouped by owner, moved to the owner and merged there
