@@ -476,6 +476,8 @@ void cfk_keys_added(void* vc, const int64_t* keys, uint64_t n, uint64_t nk, hipS
 void kl_join(ad_ctx* c);
 int cfk_miss_spare(void* vc, uint64_t n, uint64_t n_ids, uint64_t** off, uint32_t** ids);
 int cfk_miss_swap(void* vc, uint64_t** off, uint32_t** ids);
+// the ctx's store as the run_cfk_* calls take it: work area (created when absent), views, buffers, callbacks
+CfkStore cfk_store(ad_ctx* c, hipStream_t st);
 int cfk_update_run(ad_ctx* c, const CfkUpdIn& u, hipStream_t st, uint64_t* n_applied, ad_stats* stats);
 int cfk_update_follow(ad_ctx* c, const CfkUpdOut& o, int rc, hipStream_t st);
 // ids (host) joined to the device dictionary where it does not hold them; ranks[i] their member ranks (host

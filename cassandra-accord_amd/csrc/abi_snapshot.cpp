@@ -569,14 +569,11 @@ int build_snapshot_device(ad_ctx* c)
     if ((rc = set_views(c, n_dict, n_samp, last, nk, ne, hcap, rp, nrb))) return rc;
     if (n_samp) HIPCHK(c, run_dict_sample(c->ds, c->d_ds_hi.as<uint64_t>(), c->d_ds_lo.as<uint64_t>(), c->d_ds_node.as<int32_t>(), st));
     if ((rc = build_dict_buckets(c, st))) return rc;
-    if (!c->cu) c->cu = cfk_upd_work_create();
-    CfkDevState d{c->d_status.as<uint8_t>(), c->d_xrank.as<uint32_t>(), c->d_ekey.as<uint32_t>(),
-                  c->d_dict_lsb_raw.as<uint64_t>(), c->d_ballot.p ? c->d_ballot.as<Bal>() : nullptr, nullptr,
-                  c->d_ent.as<uint2>(), c->d_krec.as<KeyRec>(), c->d_kent.as<KeyEntry>()};
-    CfkDerivedBufs b{c->d_cand.as<uint32_t>(), c->d_cand.cap / 4, c->d_cwr.as<uint32_t>(), c->d_cwr.cap / 4,
-                     c->d_w.as<uint2>(), c->d_w.cap / 8};
+    CfkStore cs = cfk_store(c, st);
+    cs.d.mref = nullptr;          // the ingest builds no per-entry missing() references,
+    cs.miss.on = false;           // and the derivation reads no lists
     uint64_t bad_e = 0;
-    if ((rc = run_cfk_derive_full(c->cu, c->ds, d, &b, cfk_need_bufs, c, st, &bad_e, &e)))
+    if ((rc = run_cfk_derive_full(cs, &bad_e)))
     {
         if (rc == AD_E_DUP_EXEC)
         {
@@ -585,7 +582,7 @@ int build_snapshot_device(ad_ctx* c)
             return c->fail(rc, "CommandsForKey of key %lld violates unique committed executeAt (CommandsForKey.java:1439)",
                            k < nk ? (long long)K.keys[k] : -1ll);
         }
-        return c->fail(rc, "%s", e.c_str());
+        return c->fail(rc, "%s", cs.err.c_str());
     }
     phase("derivation + trees");
     DevSnapshot& s = c->ds;
@@ -681,37 +678,16 @@ int truncate_to_rb(ad_ctx* c, const std::vector<RbSpan>* spans)
     const bool host_lists = !c->dmiss_on && !K.miss_off.empty() && !K.miss_stale;
     if (host_lists)
         if (int rc = sync_host(c)) return rc;          // K.seg and the lists index the device's entries
-    if (!c->cu) c->cu = cfk_upd_work_create();
-    CfkDevState d{c->d_status.as<uint8_t>(), c->d_xrank.as<uint32_t>(), c->d_ekey.as<uint32_t>(),
-                  c->d_dict_lsb_raw.as<uint64_t>(), c->d_ballot.p ? c->d_ballot.as<Bal>() : nullptr,
-                  c->dmiss_on ? c->d_mref.as<uint32_t>() : nullptr,
-                  c->d_ent.as<uint2>(), c->d_krec.as<KeyRec>(), c->d_kent.as<KeyEntry>()};
-    CfkDerivedBufs b{c->d_cand.as<uint32_t>(), c->d_cand.cap / 4, c->d_cwr.as<uint32_t>(), c->d_cwr.cap / 4,
-                     c->d_w.as<uint2>(), c->d_w.cap / 8};
-    const CfkGrow grow{c, cfk_grow_dict, cfk_grow_entries, cfk_swap_entries, cfk_ballot_init, cfk_dict_spare, cfk_dict_swap,
-                       c->d_rtxw.as<uint32_t>(), c->ds.n_rent, c->d_cell_ent.as<uint64_t>(), c->ds.cell_ent ? c->n_cell_ent : 0,
-                       c->d_rb_wm.as<uint32_t>(), c->ds.n_rb, c->dmiss_on ? c->d_mids.as<uint32_t>() : nullptr,
-                       c->dmiss_on ? c->dmiss_ids : 0, cfk_keys_spare, cfk_keys_swap,
-                       c->d_kcell.p ? c->d_kcell.as<uint32_t>() : nullptr};
-    CfkMiss miss;
-    miss.on = c->dmiss_on;
-    miss.n_lists = c->dmiss_lists;
-    miss.off = c->d_moff.as<uint64_t>();
-    miss.ids = c->d_mids.as<uint32_t>();
-    miss.ctx = c;
-    miss.spare = cfk_miss_spare;
-    miss.swap = cfk_miss_swap;
+    CfkStore cs = cfk_store(c, c->stream);
     std::vector<uint32_t> pos(host_lists ? nk : 0);
     CfkTruncOut o;
-    std::string e;
-    const int rc = run_cfk_truncate(c->cu, c->ds, d, &b, cfk_need_bufs, c, grow, c->stream, &o, &e, &miss,
-                                    host_lists ? pos.data() : nullptr, spans ? c->d_rb_span.as<RbSpan>() : nullptr,
-                                    spans ? spans->size() : 0);
+    const int rc = run_cfk_truncate(cs, host_lists ? pos.data() : nullptr, spans ? c->d_rb_span.as<RbSpan>() : nullptr,
+                                    spans ? spans->size() : 0, &o);
     if (rc)
     {
         c->host_stale = true;
         c->dirty = true;
-        return c->fail(rc, "RedundantBefore truncation: %s", e.c_str());
+        return c->fail(rc, "RedundantBefore truncation: %s", cs.err.c_str());
     }
     c->n_trunc_examined += o.n_examined;
     c->ms_truncate += o.ms_total;

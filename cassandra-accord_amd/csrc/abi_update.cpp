@@ -327,6 +327,57 @@ int cfk_miss_swap(void* vc, uint64_t** off, uint32_t** ids)
     return 0;
 }
 
+// The store as the run_cfk_* calls see it, from the ctx's buffers as they stand now (build it after whatever
+// may move them: build_snapshot, dmiss_enable). A caller that deviates says so right after the call.
+CfkStore cfk_store(ad_ctx* c, hipStream_t st)
+{
+    if (!c->cu) c->cu = cfk_upd_work_create();
+    CfkStore cs{c->cu, c->ds};
+    cs.st = st;
+    cs.need = cfk_need_bufs;
+    cs.need_ctx = c;
+    CfkDevState& d = cs.d;
+    d.status = c->d_status.as<uint8_t>();
+    d.xrank = c->d_xrank.as<uint32_t>();
+    d.ekey = c->d_ekey.as<uint32_t>();
+    d.dict_lsb_raw = c->d_dict_lsb_raw.as<uint64_t>();
+    d.ballot = c->d_ballot.p ? c->d_ballot.as<Bal>() : nullptr;
+    d.mref = c->dmiss_on ? c->d_mref.as<uint32_t>() : nullptr;
+    d.ent = c->d_ent.as<uint2>();
+    d.krec = c->d_krec.as<KeyRec>();
+    d.kent = c->d_kent.as<KeyEntry>();
+    cs.bufs = CfkDerivedBufs{c->d_cand.as<uint32_t>(), c->d_cand.cap / 4, c->d_cwr.as<uint32_t>(), c->d_cwr.cap / 4,
+                             c->d_w.as<uint2>(), c->d_w.cap / 8};
+    CfkGrow& g = cs.grow;
+    g.ctx = c;
+    g.dict = cfk_grow_dict;
+    g.entries = cfk_grow_entries;
+    g.swap = cfk_swap_entries;
+    g.ballot_init = cfk_ballot_init;
+    g.dict_spare = cfk_dict_spare;
+    g.dict_swap = cfk_dict_swap;
+    g.r_txw = c->d_rtxw.as<uint32_t>();
+    g.n_rtxw = c->ds.n_rent;
+    g.cell_ent = c->d_cell_ent.as<uint64_t>();
+    g.n_cell_ent = c->ds.cell_ent ? c->n_cell_ent : 0;
+    g.rb_wm = c->d_rb_wm.as<uint32_t>();
+    g.n_rb = c->ds.n_rb;
+    g.m_ids = c->dmiss_on ? c->d_mids.as<uint32_t>() : nullptr;
+    g.n_mids = c->dmiss_on ? c->dmiss_ids : 0;
+    g.keys_spare = cfk_keys_spare;
+    g.keys_swap = cfk_keys_swap;
+    g.kcell = c->d_kcell.p ? c->d_kcell.as<uint32_t>() : nullptr;   // keys_added stays null: the update's alone
+    CfkMiss& m = cs.miss;
+    m.on = c->dmiss_on;
+    m.n_lists = c->dmiss_lists;
+    m.off = c->d_moff.as<uint64_t>();
+    m.ids = c->d_mids.as<uint32_t>();
+    m.ctx = c;
+    m.spare = cfk_miss_spare;
+    m.swap = cfk_miss_swap;
+    return cs;
+}
+
 // Start maintaining TxnInfo.missing() on the device: the host lists (NO_TXNIDS everywhere without a
 // load) as rank CSR, every entry its own list. 1: the lists cannot go to the device (stale, or an
 // id outside the dictionary): they are then marked stale by updates as before.
@@ -393,32 +444,14 @@ int cfk_update_run(ad_ctx* c, const CfkUpdIn& u, hipStream_t st, uint64_t* n_app
         if (c->host_stale == false && c->dmiss_on) { if (int rc = pull_missing(c)) return rc; }
         c->dmiss_on = false;
     }
-    if (!c->cu) c->cu = cfk_upd_work_create();
-    CfkDevState d{c->d_status.as<uint8_t>(), c->d_xrank.as<uint32_t>(), c->d_ekey.as<uint32_t>(),
-                  c->d_dict_lsb_raw.as<uint64_t>(), c->d_ballot.p ? c->d_ballot.as<Bal>() : nullptr,
-                  c->dmiss_on ? c->d_mref.as<uint32_t>() : nullptr,
-                  c->d_ent.as<uint2>(), c->d_krec.as<KeyRec>(), c->d_kent.as<KeyEntry>()};
-    CfkDerivedBufs b{c->d_cand.as<uint32_t>(), c->d_cand.cap / 4, c->d_cwr.as<uint32_t>(), c->d_cwr.cap / 4,
-                     c->d_w.as<uint2>(), c->d_w.cap / 8};
-    CfkUpdOut o;
-    std::string e;
-    const CfkGrow grow{c, cfk_grow_dict, cfk_grow_entries, cfk_swap_entries, cfk_ballot_init, cfk_dict_spare, cfk_dict_swap,
-                       c->d_rtxw.as<uint32_t>(), c->ds.n_rent, c->d_cell_ent.as<uint64_t>(), c->ds.cell_ent ? c->n_cell_ent : 0,
-                       c->d_rb_wm.as<uint32_t>(), c->ds.n_rb, c->dmiss_on ? c->d_mids.as<uint32_t>() : nullptr,
-                       c->dmiss_on ? c->dmiss_ids : 0, cfk_keys_spare, cfk_keys_swap,
-                       c->d_kcell.p ? c->d_kcell.as<uint32_t>() : nullptr, cfk_keys_added};
     if (int rc = host_dict(c)) return rc;
-    CfkMiss miss;
     host_trace("upd: host_dict");
-    miss.on = c->dmiss_on && u.dep_off;
-    miss.n_lists = c->dmiss_lists;
-    miss.off = c->d_moff.as<uint64_t>();
-    miss.ids = c->d_mids.as<uint32_t>();
-    miss.ctx = c;
-    miss.spare = cfk_miss_spare;
-    miss.swap = cfk_miss_swap;
+    CfkStore cs = cfk_store(c, st);
+    cs.grow.keys_added = cfk_keys_added;            // only an update batch starts the KeyLine hash early
+    cs.miss.on = cs.miss.on && u.dep_off;           // a batch without deps leaves the lists alone
+    CfkUpdOut o;
     c->lp_upd.clear(); c->lp_keys.clear(); c->lp_msb.clear(); c->lp_lsb.clear(); c->lp_node.clear();
-    const int rc = run_cfk_update(c->cu, c->ds, d, u, &b, cfk_need_bufs, c, grow, st, &o, &e, &miss);
+    const int rc = run_cfk_update(cs, u, &o);
     kl_join(c);
     if (!o.n_new_keys) c->kl_async = false;
     host_trace("upd: run_cfk_update");
@@ -457,8 +490,8 @@ int cfk_update_run(ad_ctx* c, const CfkUpdIn& u, hipStream_t st, uint64_t* n_app
     }
     // a failure after the explicit batch stood is AD_E_PARTIAL: a caller must not take it for "nothing
     // applied" and retry the batch
-    if (rc && o.batch_stood) return c->fail(AD_E_PARTIAL, "explicit updates applied, deps-derived part failed: %s", e.c_str());
-    if (rc) return c->fail(rc, "%s", e.c_str());
+    if (rc && o.batch_stood) return c->fail(AD_E_PARTIAL, "explicit updates applied, deps-derived part failed: %s", cs.err.c_str());
+    if (rc) return c->fail(rc, "%s", cs.err.c_str());
     if (u.n)
     {
         c->host_stale = true;
@@ -571,16 +604,8 @@ int dict_ensure_ids(ad_ctx* c, const std::vector<Tid>& ids, std::vector<uint32_t
     if (int rc = upload(c, c->d_adv_l, xl)) return rc;
     if (int rc = upload(c, c->d_adv_n, xn)) return rc;
     if (!c->d_adv_rank.ensure(4 * nx)) return c->fail(AD_E_NOMEM, "id ranks");
-    if (!c->cu) c->cu = cfk_upd_work_create();
-    CfkDevState d{c->d_status.as<uint8_t>(), c->d_xrank.as<uint32_t>(), c->d_ekey.as<uint32_t>(),
-                  c->d_dict_lsb_raw.as<uint64_t>(), c->d_ballot.p ? c->d_ballot.as<Bal>() : nullptr,
-                  c->dmiss_on ? c->d_mref.as<uint32_t>() : nullptr,
-                  c->d_ent.as<uint2>(), c->d_krec.as<KeyRec>(), c->d_kent.as<KeyEntry>()};
-    const CfkGrow grow{c, cfk_grow_dict, cfk_grow_entries, cfk_swap_entries, cfk_ballot_init, cfk_dict_spare, cfk_dict_swap,
-                       c->d_rtxw.as<uint32_t>(), c->ds.n_rent, c->d_cell_ent.as<uint64_t>(), c->ds.cell_ent ? c->n_cell_ent : 0,
-                       c->d_rb_wm.as<uint32_t>(), c->ds.n_rb, c->dmiss_on ? c->d_mids.as<uint32_t>() : nullptr,
-                       c->dmiss_on ? c->dmiss_ids : 0, cfk_keys_spare, cfk_keys_swap,
-                       c->d_kcell.p ? c->d_kcell.as<uint32_t>() : nullptr};
+    CfkStore cs = cfk_store(c, c->stream);
+    cs.miss.on = false;           // no list is rebuilt here (a merge remaps their ranks through grow.m_ids)
     // the host's per-entry copies are rebuilt from the device on demand after a merge (it remaps every rank): no
     // host remap of them here
     const bool aligned = !c->host_moved || c->host_ingested;
@@ -591,12 +616,8 @@ int dict_ensure_ids(ad_ctx* c, const std::vector<Tid>& ids, std::vector<uint32_t
     }
     c->host_stale = true;
     CfkUpdOut o;
-    std::string e;
-    CfkDerivedBufs b{c->d_cand.as<uint32_t>(), c->d_cand.cap / 4, c->d_cwr.as<uint32_t>(), c->d_cwr.cap / 4,
-                     c->d_w.as<uint2>(), c->d_w.cap / 8};
-    const int rc = run_cfk_dict_ensure(c->cu, c->ds, d, c->d_adv_m.as<uint64_t>(), c->d_adv_l.as<uint64_t>(),
-                                       c->d_adv_n.as<int32_t>(), nx, grow, &b, cfk_need_bufs, c, c->stream, &o,
-                                       c->d_adv_rank.as<uint32_t>(), &e);
+    const CfkIds dev_ids{c->d_adv_m.as<uint64_t>(), c->d_adv_l.as<uint64_t>(), c->d_adv_n.as<int32_t>(), nx};
+    const int rc = run_cfk_dict_ensure(cs, dev_ids, c->d_adv_rank.as<uint32_t>(), &o);
     if (const int frc = cfk_update_follow(c, o, rc, c->stream))
     {
         c->dirty = true;
@@ -605,7 +626,7 @@ int dict_ensure_ids(ad_ctx* c, const std::vector<Tid>& ids, std::vector<uint32_t
     if (rc)
     {
         c->dirty = true;        // rebuilt from the host copies at the next use
-        return c->fail(rc, "id dictionary growth: %s", e.c_str());
+        return c->fail(rc, "id dictionary growth: %s", cs.err.c_str());
     }
     // a merge's follow-up marks the entries as moved (an update batch's insertions); here only ranks changed
     if (aligned) c->host_ingested = true;
@@ -814,36 +835,16 @@ int ad_cfk_prune(ad_ctx* c, const int64_t* keys, uint64_t n_keys, int32_t prune_
         }
         if (int rc = upload(c, c->d_prune_keys, kl)) return rc;
     }
-    if (!c->cu) c->cu = cfk_upd_work_create();
-    CfkDevState d{c->d_status.as<uint8_t>(), c->d_xrank.as<uint32_t>(), c->d_ekey.as<uint32_t>(),
-                  c->d_dict_lsb_raw.as<uint64_t>(), c->d_ballot.p ? c->d_ballot.as<Bal>() : nullptr,
-                  c->dmiss_on ? c->d_mref.as<uint32_t>() : nullptr,
-                  c->d_ent.as<uint2>(), c->d_krec.as<KeyRec>(), c->d_kent.as<KeyEntry>()};
-    CfkDerivedBufs b{c->d_cand.as<uint32_t>(), c->d_cand.cap / 4, c->d_cwr.as<uint32_t>(), c->d_cwr.cap / 4,
-                     c->d_w.as<uint2>(), c->d_w.cap / 8};
-    const CfkGrow grow{c, cfk_grow_dict, cfk_grow_entries, cfk_swap_entries, cfk_ballot_init, cfk_dict_spare, cfk_dict_swap,
-                       c->d_rtxw.as<uint32_t>(), c->ds.n_rent, c->d_cell_ent.as<uint64_t>(), c->ds.cell_ent ? c->n_cell_ent : 0,
-                       c->d_rb_wm.as<uint32_t>(), c->ds.n_rb, c->dmiss_on ? c->d_mids.as<uint32_t>() : nullptr,
-                       c->dmiss_on ? c->dmiss_ids : 0, cfk_keys_spare, cfk_keys_swap,
-                       c->d_kcell.p ? c->d_kcell.as<uint32_t>() : nullptr};
+    CfkStore cs = cfk_store(c, c->stream);
     CfkPruneOut o;
-    std::string e;
-    CfkMiss miss;
-    miss.on = c->dmiss_on;
-    miss.n_lists = c->dmiss_lists;
-    miss.off = c->d_moff.as<uint64_t>();
-    miss.ids = c->d_mids.as<uint32_t>();
-    miss.ctx = c;
-    miss.spare = cfk_miss_spare;
-    miss.swap = cfk_miss_swap;
-    const int rc = run_cfk_prune(c->cu, c->ds, d, keys ? c->d_prune_keys.as<uint32_t>() : nullptr, keys ? kl.size() : nk,
-                                 prune_interval, min_hlc_delta, &b, cfk_need_bufs, c, grow, c->stream, &o, &e, &miss);
+    const int rc = run_cfk_prune(cs, keys ? c->d_prune_keys.as<uint32_t>() : nullptr, keys ? kl.size() : nk, prune_interval,
+                                 min_hlc_delta, &o);
     if (rc)
     {
         // the derived arrays may be half built: rebuild everything from the entries at the next use
         c->host_stale = true;
         c->dirty = true;
-        return c->fail(rc, "ad_cfk_prune: %s", e.c_str());
+        return c->fail(rc, "ad_cfk_prune: %s", cs.err.c_str());
     }
     if (o.n_removed)
     {

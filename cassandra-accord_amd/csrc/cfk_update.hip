@@ -20,16 +20,14 @@
 // it (no rank changes), otherwise merged, which remaps every stored rank in place (monotone, so all
 // rank-sorted arrays stay sorted) before the batch is located. A failed batch leaves the store's
 // content unchanged (a merged dictionary stays: it adds ids, changes no answer).
-// Pruning (run_cfk_prune, end of file): Pruning.maybePrune / pruneBefore for a list of keys, the
-// removed entries compacted out of the per-entry arrays and the derived arrays rebuilt.
+// Pruning and RedundantBefore truncation (cfk_trim.hip) remove entries; the host steps they share with
+// the update (cfk_work.hpp) are defined here, with the kernels behind them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdio>
 
-#include "../../include/accord_deps.h"
-#include "cfk_update.hpp"
-#include "devmem.hpp"
+#include "cfk_work.hpp"
 #include "kernels.hpp"
 #include "levels.hpp"
 #include "wave.hpp"
@@ -49,19 +47,6 @@ enum : uint32_t {
     UE_UNWITNESSED = 8,  // a dep the txn's kind does not witness, inside byId, absent, not an ExclusiveSyncPoint
 };
 
-struct UpdCtl {
-    uint32_t err, err_idx;
-    unsigned long long applied;
-    uint64_t tot[4];          // cand per class, committed entries
-    uint64_t tot2[2];         // new dictionary ids (unique), inserted entries (groups)
-    uint64_t tot3[2];         // insertion updates, present updates (ballot fold)
-    uint32_t n_new, n_ins;    // ids the dictionary does not hold, insertion updates
-    unsigned long long diff[3];   // OR of (word ^ reference) over the new ids: node, lo, hi (sort digits)
-    uint32_t older, pad;      // a new id is older than the newest dictionary id (dictionary merge)
-    uint64_t cm[2];           // incremental committed order: entries kept from the last one, changed committed entries
-    uint32_t n_newk, pad2;    // update keys without a CommandsForKey (with repeats)
-    unsigned long long kdiff; // OR of (key ^ the batch's first key) over them, sign-flipped (sort digits)
-};
 constexpr uint32_t LOC_NONE = 0xFFFFFFFFu;
 
 __device__ inline void upd_fail(UpdCtl* c, uint32_t code, uint32_t idx)
@@ -1115,7 +1100,6 @@ __global__ void k_ins_before(uint64_t nk, const uint32_t* gkey, uint64_t G, uint
     ib[k] = (uint32_t)lo;
 }
 
-struct EntArrays { uint2* ent; uint8_t* status; uint32_t* xrank; uint32_t* ekey; Bal* bal; uint8_t* chg; uint32_t* mref; };
 
 // an old entry moves up by the new entries before it: those of lower keys, and those of its key
 // with a lower rank (a mid-segment insert, :1002-1007)
@@ -1421,43 +1405,7 @@ __global__ __launch_bounds__(256) void k_cm_merge(uint64_t na, const uint64_t* k
     }
 }
 
-unsigned blocks(uint64_t n, unsigned t = 256) { return (unsigned)std::max<uint64_t>(1, (n + t - 1) / t); }
-
-// grows with slack (insertions raise the entry count every batch: no reallocation, and no re-zeroing
-// of `word`, per batch); zero: the whole new allocation is zeroed
-struct DBuf : DevBuf {
-    bool ensure(size_t b, bool zero = false) { return grow(b, zero); }
-};
-
 }  // namespace
-
-struct CfkUpdWork {
-    DBuf ctl, loc, xr, word, bk, flags, fs, bsum, ck, cv, ck2, cv2, hist, hoff, f2, s2, maw, wtail, kmap;
-    DBuf sm_hi, sm_lo, sm_node;
-    DBuf nw, nk_a, nk_b, nv_a, nv_b, nflag, npos, ins_k, ins_v, gflag, gs, gword, gkey, grank, ib, krec_bk;
-    DBuf mh, ml, mn, mraw, mpos;
-    DBuf bkb, uflag, upos, rk;
-    // missing() maintenance: per update applied flags, dep ranks, additions batch, derivation
-    DBuf uapp, drank, acnt, aoff, a_k, a_tm, a_tl, a_tn, a_st, dsrc, mflag, mpp, mpend, mcnt, moff;
-    // byId's last txnId as each update sees it (additions past the end) and the LoadPruned ids
-    DBuf trk, pk, pv, pk2, pv2, pvv, pw, pe, pbm, plast, ppos, lcnt, loff, l_k, l_tm, l_tl, l_tn, l_i;
-    DBuf kn_a, kn_b, kv_a, kv_b, kflag, kfpos, knew, kpos;   // new keys
-    DBuf tpos, twm, ids_st, ids_rank;                          // RedundantBefore truncation / dictionary ensure
-    // incremental committed order: the last derivation's order (entry indices), per-entry changed
-    // flags (double-buffered with the entry arrays), the insertion's old -> new entry map
-    DBuf cm, chg[2], mv, af, ap, bfl, bps, cka, cva, ckb, cvb, ckb2, cvb2;
-    int chg_cur = 0;
-    uint64_t cm_n = 0;
-    bool cm_valid = false, moved = false;
-    UpdCtl* h_ctl = nullptr;
-    hipEvent_t ev[3] = {};
-    ~CfkUpdWork()
-    {
-        if (h_ctl) (void)hipHostFree(h_ctl);
-        for (auto& e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
 
 CfkUpdWork* cfk_upd_work_create() { return new CfkUpdWork(); }
 void cfk_upd_work_invalidate(CfkUpdWork* w)
@@ -1473,28 +1421,61 @@ static uint32_t bytes_of(uint64_t v)
     return b;
 }
 
-#define UCHK(expr)                                                                                \
-    do {                                                                                          \
-        hipError_t _e = (expr);                                                                   \
-        if (_e != hipSuccess) { *err = std::string(#expr) + ": " + hipGetErrorString(_e); return AD_E_DEVICE; } \
-    } while (0)
-#define UALLOC_V(buf, bytes)                                                                      \
-    do {                                                                                          \
-        if (!(buf).ensure((bytes), false)) return DictSample{nullptr, nullptr, nullptr, 0};       \
-    } while (0)
-#define UALLOC(buf, bytes, zero)                                                                  \
-    do {                                                                                          \
-        if (!(buf).ensure((bytes), (zero))) { *err = "device allocation (cfk update)"; return AD_E_NOMEM; } \
-    } while (0)
-
-static uint32_t key_rank_mask(uint64_t n_dict, uint64_t nk);
-
-// Rebuild ent.tau, cand, cwr, w, krec, kent and the trees from the per-entry state (status,
-// executeAt rank). A duplicate committed executeAt is reported in ctl->err.
-static int cfk_derive(CfkUpdWork* w, DevSnapshot& s, const CfkDevState& dd, CfkDerivedBufs* bufs,
-                      int (*need)(void*, uint64_t, uint64_t, uint64_t, CfkDerivedBufs*), void* need_ctx, hipStream_t st,
-                      std::string* err, bool incr = false)
+// the radix digits a (key index << 32 | rank) sort needs
+static uint32_t key_rank_mask(uint64_t n_dict, uint64_t nk)
 {
+    uint32_t mask = 0;
+    const uint32_t xb = bytes_of(2 * n_dict + 1), kb = bytes_of(nk ? nk - 1 : 0);
+    for (uint32_t b = 0; b < xb && b < 4; ++b) mask |= 1u << b;
+    for (uint32_t b = 0; b < kb && b < 4; ++b) mask |= 1u << (4 + b);
+    return mask;
+}
+
+int cfk_begin(CfkStore& cs)
+{
+    CfkUpdWork* w = cs.w;
+    if (!w->h_ctl && hipHostMalloc((void**)&w->h_ctl, sizeof(UpdCtl)) != hipSuccess) { cs.err = "pinned ctl"; return AD_E_NOMEM; }
+    for (auto& e : w->ev)
+        if (!e) UCHK(timing_event(&e));
+    UALLOC(w->ctl, sizeof(UpdCtl), false);
+    UCHK(hipMemsetAsync(w->ctl.p, 0, sizeof(UpdCtl), cs.st));
+    UCHK(hipEventRecord(w->ev[0], cs.st));
+    return AD_OK;
+}
+
+int cfk_elapsed(CfkStore& cs, double* ms)
+{
+    CfkUpdWork* w = cs.w;
+    UCHK(hipEventRecord(w->ev[1], cs.st));
+    UCHK(hipEventSynchronize(w->ev[1]));
+    float a = 0;
+    (void)hipEventElapsedTime(&a, w->ev[0], w->ev[1]);
+    *ms = a;
+    return AD_OK;
+}
+
+// The sampled dictionary (every SAMP-th id) of the current s.n_dict, queued on the stream.
+static int dict_sample(CfkStore& cs, DictSample* ds)
+{
+    CfkUpdWork* w = cs.w;
+    const uint64_t n_samp = (cs.s.n_dict + SAMP - 1) / SAMP;
+    UALLOC(w->sm_hi, 8 * std::max<uint64_t>(n_samp, 1), false);
+    UALLOC(w->sm_lo, 8 * std::max<uint64_t>(n_samp, 1), false);
+    UALLOC(w->sm_node, 4 * std::max<uint64_t>(n_samp, 1), false);
+    if (n_samp)
+        k_dict_sample<<<blocks(n_samp), 256, 0, cs.st>>>(cs.s, w->sm_hi.as<uint64_t>(), w->sm_lo.as<uint64_t>(),
+                                                         w->sm_node.as<int32_t>(), n_samp);
+    *ds = DictSample{w->sm_hi.as<uint64_t>(), w->sm_lo.as<uint64_t>(), w->sm_node.as<int32_t>(), n_samp};
+    return AD_OK;
+}
+
+int cfk_derive(CfkStore& cs, bool incr)
+{
+    CfkUpdWork* w = cs.w;
+    DevSnapshot& s = cs.s;
+    const CfkDevState& dd = cs.d;
+    CfkDerivedBufs* bufs = &cs.bufs;
+    const hipStream_t st = cs.st;
     const uint64_t ne = s.n_ent, nk = s.n_keys;
     UpdCtl* ctl = w->ctl.as<UpdCtl>();
     const uint64_t sb = (std::max<uint64_t>(ne, 1) + 1023) / 1024 + 8;
@@ -1533,7 +1514,7 @@ static int cfk_derive(CfkUpdWork* w, DevSnapshot& s, const CfkDevState& dd, CfkD
     host_trace("derive: totals sync");
     const uint64_t nA = inc ? w->h_ctl->cm[0] : 0, nB = inc ? w->h_ctl->cm[1] : 0;
     const bool use_inc = inc && nA + nB == ncm;     // else (never expected) the full sort
-    int rc = need(need_ctx, n_cand, ncm, ncm, bufs);
+    int rc = cs.need(cs.need_ctx, n_cand, ncm, ncm, bufs);
     if (rc) return rc;
     UALLOC(w->ck, 8 * std::max<uint64_t>(ncm, 1), false);
     UALLOC(w->cv, 4 * std::max<uint64_t>(ncm, 1), false);
@@ -1621,21 +1602,15 @@ static int cfk_derive(CfkUpdWork* w, DevSnapshot& s, const CfkDevState& dd, CfkD
     return AD_OK;
 }
 
-// the radix digits a (key index << 32 | rank) sort needs
-static uint32_t key_rank_mask(uint64_t n_dict, uint64_t nk)
-{
-    uint32_t mask = 0;
-    const uint32_t xb = bytes_of(2 * n_dict + 1), kb = bytes_of(nk ? nk - 1 : 0);
-    for (uint32_t b = 0; b < xb && b < 4; ++b) mask |= 1u << b;
-    for (uint32_t b = 0; b < kb && b < 4; ++b) mask |= 1u << (4 + b);
-    return mask;
-}
-
 // Keys of the batch without a CommandsForKey: merged into the key arrays (spare buffers), entry key
 // indices remapped, key hash rebuilt.
-static int add_keys(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const CfkUpdIn& u, const CfkGrow& grow, hipStream_t st,
-                    CfkUpdOut* out, std::string* err)
+static int add_keys(CfkStore& cs, const CfkUpdIn& u, CfkUpdOut* out)
 {
+    CfkUpdWork* w = cs.w;
+    DevSnapshot& s = cs.s;
+    CfkDevState& d = cs.d;
+    const CfkGrow& grow = cs.grow;
+    const hipStream_t st = cs.st;
     const uint64_t n = u.n, nk = s.n_keys, ne = s.n_ent;
     UpdCtl* ctl = w->ctl.as<UpdCtl>();
     UALLOC(w->kn_a, 8 * n, false);
@@ -1674,13 +1649,13 @@ static int add_keys(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const CfkUpdI
     UCHK(hipStreamSynchronize(st));
     const uint64_t U = w->h_ctl->tot3[0];
     host_trace("add_keys: sort+unique sync");
-    if (nk + U >= KEY_EMPTY) { *err = "more than 2^32-1 keys"; return AD_E_CAPACITY; }
+    if (nk + U >= KEY_EMPTY) { cs.err = "more than 2^32-1 keys"; return AD_E_CAPACITY; }
     UALLOC(w->knew, 8 * U, false);
     UALLOC(w->kpos, 8 * U, false);
     k_key_place<<<blocks(m), 256, 0, st>>>(s, ks, m, w->kflag.as<uint32_t>(), w->kfpos.as<uint64_t>(), w->knew.as<int64_t>(),
                                            w->kpos.as<uint64_t>());
     KeyBufs nb{};
-    if (int rc = grow.keys_spare(grow.ctx, nk + U, &nb)) { *err = "key arrays"; return rc; }
+    if (int rc = grow.keys_spare(grow.ctx, nk + U, &nb)) { cs.err = "key arrays"; return rc; }
     host_trace("add_keys: keys_spare");
     const uint64_t* kpos = w->kpos.as<uint64_t>();
     UALLOC(w->kmap, 4 * std::max<uint64_t>(nk, 1), false);
@@ -1690,7 +1665,7 @@ static int add_keys(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const CfkUpdI
     k_khash_clear<<<blocks(nb.hcap), 256, 0, st>>>(nb.khash, nb.hcap);
     k_khash_fill<<<blocks(nk + U), 256, 0, st>>>(nk + U, nb);
     UCHK(hipGetLastError());
-    if (int rc = grow.keys_swap(grow.ctx, &nb)) { *err = "key arrays"; return rc; }
+    if (int rc = grow.keys_swap(grow.ctx, &nb)) { cs.err = "key arrays"; return rc; }
     UCHK(hipStreamSynchronize(st));
     host_trace("add_keys: move+swap sync");
     if (grow.keys_added) grow.keys_added(grow.ctx, w->knew.as<int64_t>(), U, nk + U, st);
@@ -1710,10 +1685,14 @@ static int add_keys(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const CfkUpdI
 
 // Merge the sorted unique new ids (nflag/npos over the sorted order vs) into the dictionary: new
 // arrays (spare buffers), then every stored rank remapped in place.
-static int merge_dictionary(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const DictSample& ds, const CfkGrow& grow,
-                            const uint32_t* vs, uint64_t m, uint64_t cap, uint64_t U, hipStream_t st, CfkUpdOut* out,
-                            std::string* err)
+static int merge_dictionary(CfkStore& cs, const DictSample& ds, const uint32_t* vs, uint64_t m, uint64_t cap, uint64_t U,
+                            CfkUpdOut* out)
 {
+    CfkUpdWork* w = cs.w;
+    DevSnapshot& s = cs.s;
+    CfkDevState& d = cs.d;
+    const CfkGrow& grow = cs.grow;
+    const hipStream_t st = cs.st;
     const uint64_t n0 = s.n_dict, ne = s.n_ent, nk = s.n_keys;
     UALLOC(w->mh, 8 * U, false);
     UALLOC(w->ml, 8 * U, false);
@@ -1725,7 +1704,7 @@ static int merge_dictionary(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const
                                             w->mh.as<uint64_t>(), w->ml.as<uint64_t>(), w->mn.as<int32_t>(), w->mraw.as<uint64_t>());
     k_merge_pos<<<blocks(U), 256, 0, st>>>(s, ds, U, w->mh.as<uint64_t>(), w->ml.as<uint64_t>(), w->mn.as<int32_t>(), mpos);
     DictArrays nd{};
-    if (int rc = grow.dict_spare(grow.ctx, n0 + U, &nd.hi, &nd.lo, &nd.node, &nd.raw)) { *err = "dictionary merge"; return rc; }
+    if (int rc = grow.dict_spare(grow.ctx, n0 + U, &nd.hi, &nd.lo, &nd.node, &nd.raw)) { cs.err = "dictionary merge"; return rc; }
     if (n0) k_merge_old<<<blocks(n0), 256, 0, st>>>(s, d.dict_lsb_raw, mpos, U, nd);
     k_merge_new<<<blocks(U), 256, 0, st>>>(U, w->mh.as<uint64_t>(), w->ml.as<uint64_t>(), w->mn.as<int32_t>(),
                                            w->mraw.as<uint64_t>(), mpos, nd);
@@ -1736,7 +1715,7 @@ static int merge_dictionary(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const
     if (grow.n_rb) k_remap_txw<<<blocks(grow.n_rb), 256, 0, st>>>(grow.n_rb, grow.rb_wm, mpos, U);
     if (grow.n_mids) k_remap_txw<<<blocks(grow.n_mids), 256, 0, st>>>(grow.n_mids, grow.m_ids, mpos, U);
     UCHK(hipGetLastError());
-    if (int rc = grow.dict_swap(grow.ctx, &nd.hi, &nd.lo, &nd.node, &nd.raw)) { *err = "dictionary merge"; return rc; }
+    if (int rc = grow.dict_swap(grow.ctx, &nd.hi, &nd.lo, &nd.node, &nd.raw)) { cs.err = "dictionary merge"; return rc; }
     uint64_t lh = 0, ll = 0;
     int32_t ln = 0;
     UCHK(d2h(&lh, nd.hi + n0 + U - 1, 8, st));
@@ -1759,9 +1738,13 @@ static int merge_dictionary(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const
 
 // Add the batch's ids the dictionary does not hold (sorted, unique): appended when all are newer
 // than its newest id, merged otherwise.
-static int grow_dictionary(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const DictSample& ds, const CfkUpdIn& u,
-                           const CfkGrow& grow, hipStream_t st, CfkUpdOut* out, std::string* err, uint64_t ndep = 0)
+static int grow_dictionary(CfkStore& cs, const DictSample& ds, const CfkUpdIn& u, CfkUpdOut* out, uint64_t ndep = 0)
 {
+    CfkUpdWork* w = cs.w;
+    DevSnapshot& s = cs.s;
+    CfkDevState& d = cs.d;
+    const CfkGrow& grow = cs.grow;
+    const hipStream_t st = cs.st;
     const uint64_t n = u.n, cap = 2 * n + ndep;
     UpdCtl* ctl = w->ctl.as<UpdCtl>();
     UALLOC(w->nw, 8 * 4 * cap, false);
@@ -1811,11 +1794,11 @@ static int grow_dictionary(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const 
     UCHK(hipStreamSynchronize(st));
     if (w->h_ctl->err) return AD_OK;          // reported by the caller
     const uint64_t U = w->h_ctl->tot2[0], n0 = s.n_dict;
-    if (n0 + U > MAX_DICT) { *err = "id dictionary exceeds 2^28 entries"; return AD_E_CAPACITY; }
-    if (w->h_ctl->older) return merge_dictionary(w, s, d, ds, grow, vs, m, cap, U, st, out, err);
+    if (n0 + U > MAX_DICT) { cs.err = "id dictionary exceeds 2^28 entries"; return AD_E_CAPACITY; }
+    if (w->h_ctl->older) return merge_dictionary(cs, ds, vs, m, cap, U, out);
     uint64_t *dh, *dl, *draw;
     int32_t* dn;
-    if (int rc = grow.dict(grow.ctx, n0, n0 + U, &dh, &dl, &dn, &draw)) { *err = "dictionary growth"; return rc; }
+    if (int rc = grow.dict(grow.ctx, n0, n0 + U, &dh, &dl, &dn, &draw)) { cs.err = "dictionary growth"; return rc; }
     k_ins_append<<<blocks(m), 256, 0, st>>>(vs, m, nw, cap, w->nflag.as<uint32_t>(), w->npos.as<uint64_t>(), n0, dh, dl, dn,
                                             draw);
     UCHK(hipGetLastError());
@@ -1844,10 +1827,13 @@ struct InsUndo {
     bool swapped = false;       // the per-entry arrays were swapped to the spare buffers
 };
 
-static int insert_entries(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const CfkUpdIn& u, const CfkGrow& grow,
-                          hipStream_t st, uint64_t q, uint64_t* G_out, InsUndo* undo, std::string* err, bool fold,
-                          uint8_t* uapp)
+static int insert_entries(CfkStore& cs, const CfkUpdIn& u, uint64_t q, uint64_t* G_out, InsUndo* undo, bool fold, uint8_t* uapp)
 {
+    CfkUpdWork* w = cs.w;
+    DevSnapshot& s = cs.s;
+    CfkDevState& d = cs.d;
+    const CfkGrow& grow = cs.grow;
+    const hipStream_t st = cs.st;
     const uint64_t ne = s.n_ent, nk = s.n_keys;
     UpdCtl* ctl = w->ctl.as<UpdCtl>();
     UALLOC(w->ck, 8 * q, false);
@@ -1875,7 +1861,7 @@ static int insert_entries(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const C
     UCHK(d2h(w->h_ctl, ctl, sizeof(UpdCtl), st));
     UCHK(hipStreamSynchronize(st));
     const uint64_t G = w->h_ctl->tot2[1];
-    if (ne + G >= (1ull << 32)) { *err = "more than 2^32 CommandsForKey entries"; return AD_E_CAPACITY; }
+    if (ne + G >= (1ull << 32)) { cs.err = "more than 2^32 CommandsForKey entries"; return AD_E_CAPACITY; }
     UALLOC(w->gword, 8 * G, false);
     UALLOC(w->gkey, 4 * G, false);
     UALLOC(w->grank, 4 * G, false);
@@ -1895,7 +1881,7 @@ static int insert_entries(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const C
     UALLOC(w->mv, 4 * std::max<uint64_t>(ne, 1), false);
     EntArrays a{d.ent, d.status, d.xrank, d.ekey, d.ballot, w->chg[w->chg_cur].as<uint8_t>(), d.mref}, b{};
     b.chg = w->chg[w->chg_cur ^ 1].as<uint8_t>();
-    if (int rc = grow.entries(grow.ctx, ne + G, &b.ent, &b.status, &b.xrank, &b.ekey, &b.bal, &b.mref)) { *err = "entry growth"; return rc; }
+    if (int rc = grow.entries(grow.ctx, ne + G, &b.ent, &b.status, &b.xrank, &b.ekey, &b.bal, &b.mref)) { cs.err = "entry growth"; return rc; }
     const uint64_t padded = std::max<uint64_t>(64, (ne + G + 63) / 64 * 64);
     if (padded > ne + G) UCHK(hipMemsetAsync(b.ent + ne + G, 0, sizeof(uint2) * (padded - ne - G), st));
     if (ne) k_ins_move_old<<<blocks(ne), 256, 0, st>>>(ne, a, w->ib.as<uint32_t>(), w->grank.as<uint32_t>(), b, w->mv.as<uint32_t>());
@@ -1912,269 +1898,89 @@ static int insert_entries(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const C
     undo->swapped = true;         // the buffers are exchanged even when sizing the trees then failed
     w->chg_cur ^= 1;              // the changed flags moved with the entries
     w->moved = true;
-    if (src) { *err = "entry swap"; return src; }
+    if (src) { cs.err = "entry swap"; return src; }
     s.ent = d.ent;
     s.n_ent = ne + G;
     *G_out = G;
     return AD_OK;
 }
 
-static int miss_after_batch(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const CfkUpdIn& u, uint64_t ndep,
-                            CfkDerivedBufs* bufs, int (*need)(void*, uint64_t, uint64_t, uint64_t, CfkDerivedBufs*),
-                            void* need_ctx, const CfkGrow& grow, hipStream_t st, CfkUpdOut* out, std::string* err,
-                            CfkMiss* miss);
-
-int run_cfk_update(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const CfkUpdIn& u, CfkDerivedBufs* bufs,
-                   int (*need)(void*, uint64_t, uint64_t, uint64_t, CfkDerivedBufs*), void* need_ctx, const CfkGrow& grow,
-                   hipStream_t st, CfkUpdOut* out, std::string* err, CfkMiss* miss)
+int rebuild_missing_lists(CfkStore& cs, uint64_t n, const std::function<void(uint32_t*)>& count,
+                          const std::function<void(const uint64_t*, uint32_t*)>& emit)
 {
-    const uint64_t n = u.n;
-    *out = CfkUpdOut{};
-    if (n == 0) return AD_OK;
-    // missing() maintenance (with the deps of the batch): the updates fold in batch order, so each
-    // update knows whether it applied and which one an entry's TxnInfo comes from
-    const bool track = miss && miss->on && u.dep_off && d.mref;
-    uint64_t ndep = 0;
-    if (track)
-    {
-        dev_quiesce();
-        if (d2h(&ndep, u.dep_off + n, 8, dev_scope_stream()) != hipSuccess) { *err = "dep_off"; return AD_E_DEVICE; }
-        UALLOC(w->uapp, n, false);
-        UCHK(hipMemsetAsync(w->uapp.p, 0, n, st));
-    }
-    if (n >= 0x7FFFFFFFull) { *err = "more than 2^31-2 updates in one batch"; return AD_E_INVAL; }
-    if (!w->h_ctl && hipHostMalloc((void**)&w->h_ctl, sizeof(UpdCtl)) != hipSuccess) { *err = "pinned ctl"; return AD_E_NOMEM; }
-    for (auto& e : w->ev)
-        if (!e) UCHK(timing_event(&e));
-    auto describe = [&](uint32_t code, uint32_t idx) -> int {
-        char b[256];
-        const char* what = "";
-        int rc = AD_E_INVAL;
-        switch (code)
-        {
-            case UE_KEY: what = "key missing from the key arrays after its creation (internal)"; rc = AD_E_STATE; break;
-            case UE_STATUS: what = "status is not an InternalStatus ordinal"; break;
-            case UE_ABSENT: what = "txnId missing from the id dictionary after its merge (internal)"; rc = AD_E_STATE; break;
-            case UE_NEW_EXEC: what = "executeAt missing from the id dictionary after its merge (internal)"; rc = AD_E_STATE; break;
-            case UE_FLAGS: what = "ids equal under Timestamp.equals differ in flag bits"; rc = AD_E_INCONSISTENT_ID; break;
-            case UE_DOMAIN: what = "live range-domain TxnId in a CommandsForKey"; break;
-            case UE_DUP_EXEC: what = "two committed entries of one key share an executeAt (CommandsForKey.java:1439)"; rc = AD_E_DUP_EXEC; break;
-        }
-        snprintf(b, sizeof(b), "cfk update %u: %s", idx, what);
-        *err = b;
-        return rc;
-    };
-    UALLOC(w->ctl, sizeof(UpdCtl), false);
-    UALLOC(w->loc, 4 * n, false);
-    UALLOC(w->xr, 4 * n, false);
-    UALLOC(w->bk, 8 * n, false);
-    UALLOC(w->ins_k, 8 * n, false);
-    UALLOC(w->ins_v, 4 * n, false);
-    UALLOC(w->word, 8 * std::max<uint64_t>(s.n_ent, 1), true);   // zero between batches (winners clear theirs)
-    UpdCtl* ctl = w->ctl.as<UpdCtl>();
-    UCHK(hipMemsetAsync(ctl, 0, sizeof(UpdCtl), st));
-    UCHK(hipEventRecord(w->ev[0], st));
-    // per-entry changed flags of this batch (incremental committed order) and no insertion map yet
-    UALLOC(w->chg[w->chg_cur], std::max<uint64_t>(s.n_ent, 1), false);
-    if (s.n_ent) UCHK(hipMemsetAsync(w->chg[w->chg_cur].p, 0, s.n_ent, st));
-    w->moved = false;
-
-    // ---- 0. ids the dictionary does not hold join it. Ids newer than all of it are appended (no
-    // rank changes): a batch that then fails drops them again (the arrays keep the bytes; nothing
-    // refers to them). Older ones are merged with a rank remap of every stored rank: the merge
-    // stands when the batch then fails (it changes no content), and the derived arrays are rebuilt.
-    const uint64_t nd0 = s.n_dict, lh0 = s.dict_last_hi, ll0 = s.dict_last_lo;
-    const int32_t ln0 = s.dict_last_node;
-    auto drop_new_ids = [&](int code) -> int {
-        if (out->merged) return code;
-        s.n_dict = nd0;
-        s.dict_last_hi = lh0;
-        s.dict_last_lo = ll0;
-        s.dict_last_node = ln0;
-        out->n_new_ids = 0;
-        return code;
-    };
-    UALLOC(w->sm_hi, 8 * std::max<uint64_t>((s.n_dict + n + n + SAMP - 1) / SAMP, 1), false);
-    UALLOC(w->sm_lo, 8 * std::max<uint64_t>((s.n_dict + n + n + SAMP - 1) / SAMP, 1), false);
-    UALLOC(w->sm_node, 4 * std::max<uint64_t>((s.n_dict + n + n + SAMP - 1) / SAMP, 1), false);
-    auto sample = [&]() -> DictSample {
-        const uint64_t n_samp = (s.n_dict + SAMP - 1) / SAMP;
-        if (n_samp)
-            k_dict_sample<<<blocks(n_samp), 256, 0, st>>>(s, w->sm_hi.as<uint64_t>(), w->sm_lo.as<uint64_t>(),
-                                                          w->sm_node.as<int32_t>(), n_samp);
-        return DictSample{w->sm_hi.as<uint64_t>(), w->sm_lo.as<uint64_t>(), w->sm_node.as<int32_t>(), n_samp};
-    };
-    // a failure after a merge or new keys: the entries are as they were, under the new ranks /
-    // key indices; derive again
-    auto rederive = [&](int code) -> int {
-        if (!out->merged && !out->n_new_keys) return code;
-        std::string e2;
-        if (hipMemsetAsync(ctl, 0, sizeof(UpdCtl), st) != hipSuccess) { *err += "; re-derivation failed"; return AD_E_DEVICE; }
-        if (int rc2 = cfk_derive(w, s, d, bufs, need, need_ctx, st, &e2)) { *err += "; re-derivation: " + e2; return rc2; }
-        if (hipStreamSynchronize(st) != hipSuccess) { *err += "; re-derivation failed"; return AD_E_DEVICE; }
-        out->rederived = true;
-        return code;
-    };
-    if (int rc = add_keys(w, s, d, u, grow, st, out, err)) return rc == AD_E_CAPACITY ? rc : rederive(rc);
-    host_trace("upd: add_keys");
-    if (out->n_new_keys) UCHK(hipMemsetAsync(ctl, 0, sizeof(UpdCtl), st));
-    {
-        const DictSample ds0 = sample();
-        if (int rc = grow_dictionary(w, s, d, ds0, u, grow, st, out, err, ndep))
-            return rc == AD_E_CAPACITY ? drop_new_ids(rc) : rederive(rc);
-    }
-    if (w->h_ctl->err) return rederive(drop_new_ids(describe(w->h_ctl->err, w->h_ctl->err_idx)));
-
-    // ---- 1. locate and validate; nothing changes unless the whole batch is valid
-    const DictSample dsm = sample();
-    const bool bm = u.bal_msb != nullptr;
-    const bool fold = bm || track;
-    const int nf = fold ? 2 : 1;
-    if (track) UALLOC(w->trk, 4ull * 3 * n, false);
-    UALLOC(w->uflag, 4ull * 2 * n, false);
-    UALLOC(w->upos, 8ull * 2 * (n + 1), false);
-    UALLOC(w->bsum, 8ull * 2 * ((n + 1023) / 1024 + 8), false);
-    k_upd_locate<<<blocks(n), 256, 0, st>>>(s, dsm, d, u, w->loc.as<uint32_t>(), w->xr.as<uint32_t>(),
-                                            w->word.as<unsigned long long>(), w->ins_k.as<uint64_t>(),
-                                            w->uflag.as<uint32_t>(), w->rk.as<uint32_t>(), out->merge_pos,
-                                            out->merged ? out->n_new_ids : 0, ctl, fold ? 1 : 0,
-                                            track ? w->trk.as<uint32_t>() : nullptr);
-    UCHK(hipGetLastError());
-    UCHK(run_scan_arrays(w->uflag.as<uint32_t>(), w->upos.as<uint64_t>(), n, nf, w->bsum.as<uint64_t>(), st));
-    k_drv_totals<<<1, 64, 0, st>>>(w->upos.as<uint64_t>(), n, nf, ctl->tot3);
-    UCHK(d2h(w->h_ctl, ctl, sizeof(UpdCtl), st));
+    CfkUpdWork* w = cs.w;
+    CfkMiss& miss = cs.miss;
+    const hipStream_t st = cs.st;
+    UALLOC(w->mcnt, 4 * std::max<uint64_t>(n, 1), false);
+    UALLOC(w->moff, 8 * (n + 1), false);
+    UALLOC(w->bsum, 8 * ((n + 1023) / 1024 + 8), false);
+    if (n) count(w->mcnt.as<uint32_t>());
+    UCHK(run_scan_arrays(w->mcnt.as<uint32_t>(), w->moff.as<uint64_t>(), n, 1, w->bsum.as<uint64_t>(), st));
+    uint64_t nm = 0;
+    UCHK(d2h(&nm, w->moff.as<uint64_t>() + n, 8, st));
     UCHK(hipStreamSynchronize(st));
-    if (w->h_ctl->err)
+    uint64_t* noff = nullptr;
+    uint32_t* nids = nullptr;
+    if (int rc = miss.spare(miss.ctx, n, nm, &noff, &nids)) { cs.err = "missing() lists"; return rc; }
+    UCHK(hipMemcpyAsync(noff, w->moff.p, 8 * (n + 1), hipMemcpyDeviceToDevice, st));
+    if (n)
     {
-        k_upd_release<<<blocks(n), 256, 0, st>>>(n, w->loc.as<uint32_t>(), w->word.as<unsigned long long>());
-        UCHK(hipStreamSynchronize(st));
-        return rederive(drop_new_ids(describe(w->h_ctl->err, w->h_ctl->err_idx)));
+        emit(noff, nids);
+        k_mref_identity<<<blocks(n), 256, 0, st>>>(n, cs.d.mref);
     }
-    const uint64_t q = w->h_ctl->tot3[0], mp = fold ? w->h_ctl->tot3[1] : 0, ne0 = s.n_ent;
-    // the batch's first ballots: the store's entries all hold Ballot.ZERO until now
-    if (bm && !d.ballot && ne0)
-        if (int rc = grow.ballot_init(grow.ctx, ne0, &d.ballot)) { *err = "ballot array"; return rederive(drop_new_ids(rc)); }
-    const uint64_t cq = std::max<uint64_t>(std::max(q, mp), 1);
-    UALLOC(w->ck, 8 * cq, false);
-    UALLOC(w->cv, 4 * cq, false);
-    UALLOC(w->ck2, 8 * cq, false);
-    UALLOC(w->cv2, 4 * cq, false);
-    UALLOC(w->bkb, sizeof(Bal) * n, false);
-    UCHK(hipMemsetAsync(w->bk.p, 0xFF, 8 * n, st));          // bk[i].x = none: nothing to roll back
-    if (fold)
-    {
-        if (mp)
-        {
-            // the present entries' updates, sorted by entry (stable: batch order within), folded
-            uint64_t* ks = w->ck.as<uint64_t>();
-            uint32_t* vs = w->cv.as<uint32_t>();
-            k_compact<<<blocks(n), 256, 0, st>>>(n, w->uflag.as<uint32_t>() + n, w->upos.as<uint64_t>() + (n + 1), nullptr,
-                                                 w->loc.as<uint32_t>(), ks, vs);
-            if (mp > 1)
-            {
-                const uint64_t hist_n = radix_hist_entries(mp);
-                UALLOC(w->hist, 4 * hist_n, false);
-                UALLOC(w->hoff, 8 * (hist_n + 1), false);
-                UALLOC(w->bsum, 8 * ((std::max(hist_n, mp) + 1023) / 1024 + 8), false);
-                uint32_t mask = 0;
-                for (uint32_t b = 0; b < bytes_of(ne0 ? ne0 - 1 : 0) && b < 4; ++b) mask |= 1u << b;
-                if (mask)
-                    UCHK(radix_sort_pairs(ks, vs, w->ck2.as<uint64_t>(), w->cv2.as<uint32_t>(), mp, mask, w->hist.as<uint32_t>(),
-                                          w->hoff.as<uint64_t>(), w->bsum.as<uint64_t>(), st, &ks, &vs));
-            }
-            k_fold_present<<<blocks(mp), 256, 0, st>>>(mp, ks, vs, u, w->xr.as<uint32_t>(), d, w->bk.as<uint2>(),
-                                                       w->bkb.as<Bal>(), w->chg[w->chg_cur].as<uint8_t>(), ctl,
-                                                       track ? w->uapp.as<uint8_t>() : nullptr);
-        }
-    }
-    else
-        k_upd_apply<<<blocks(n), 256, 0, st>>>(n, w->loc.as<uint32_t>(), w->xr.as<uint32_t>(), w->word.as<unsigned long long>(),
-                                               d, w->bk.as<uint2>(), w->bkb.as<Bal>(), w->chg[w->chg_cur].as<uint8_t>(), ctl);
     UCHK(hipGetLastError());
-    if (q)   // the insertion updates in batch order, for insert_entries
-        k_compact<<<blocks(n), 256, 0, st>>>(n, w->uflag.as<uint32_t>(), w->upos.as<uint64_t>(), w->ins_k.as<uint64_t>(),
-                                             nullptr, w->ck.as<uint64_t>(), w->cv.as<uint32_t>());
-    // From here on the per-entry state has changed: every failure undoes the batch (status and
-    // executeAt restored, insertions swapped back, krec restored) and derives the previous state
-    // again, so that nothing changes unless the whole batch is applied.
-    InsUndo undo;
-    auto rollback = [&](int code) -> int {
-        std::string e2;
-        if (undo.swapped)
-        {
-            if (grow.swap(grow.ctx, ne0, &d.ent, &d.status, &d.xrank, &d.ekey, &d.ballot, &d.mref)) { *err += "; rollback failed"; return AD_E_DEVICE; }
-            s.ent = d.ent;
-            s.n_ent = ne0;
-        }
-        if (undo.krec_saved && s.n_keys)
-            if (hipMemcpyAsync(d.krec, w->krec_bk.p, sizeof(KeyRec) * s.n_keys, hipMemcpyDeviceToDevice, st) != hipSuccess)
-            { *err += "; rollback failed"; return AD_E_DEVICE; }
-        k_upd_rollback<<<blocks(n), 256, 0, st>>>(n, w->loc.as<uint32_t>(), w->bk.as<uint2>(), w->bkb.as<Bal>(), d);
-        if (hipGetLastError() != hipSuccess || hipMemsetAsync(ctl, 0, sizeof(UpdCtl), st) != hipSuccess)
-        { *err += "; rollback failed"; return AD_E_DEVICE; }
-        if (int rc2 = cfk_derive(w, s, d, bufs, need, need_ctx, st, &e2)) { *err += "; rollback: " + e2; return rc2; }
-        if (hipStreamSynchronize(st) != hipSuccess) { *err += "; rollback failed"; return AD_E_DEVICE; }
-        out->n_applied = out->n_inserted = 0;
-        out->rolled_back = true;
-        return drop_new_ids(code);
-    };
-    uint64_t G = 0;
-    if (q)
-        if (int rc = insert_entries(w, s, d, u, grow, st, q, &G, &undo, err, fold, track ? w->uapp.as<uint8_t>() : nullptr))
-            return rollback(rc);
-    UCHK(hipEventRecord(w->ev[1], st));
-
-    // ---- 2. re-derive the snapshot arrays from the per-entry state (committed order incrementally)
-    if (int rc = cfk_derive(w, s, d, bufs, need, need_ctx, st, err, true)) return rollback(rc);
-    UCHK(hipEventRecord(w->ev[2], st));
-    UCHK(d2h(w->h_ctl, ctl, sizeof(UpdCtl), st));
     UCHK(hipStreamSynchronize(st));
-    host_trace("upd: derive sync");
-    float a = 0, b = 0;
-    (void)hipEventElapsedTime(&a, w->ev[0], w->ev[1]);
-    (void)hipEventElapsedTime(&b, w->ev[1], w->ev[2]);
-    out->ms_locate = a;
-    out->ms_derive = b;
-    out->ms_total = a + b;
-    out->n_applied = w->h_ctl->applied + G;
-    out->n_inserted = G;
-    // a duplicate committed executeAt: undo the batch and derive the previous state again
-    if (w->h_ctl->err) return rollback(describe(w->h_ctl->err, w->h_ctl->err_idx));
-    out->batch_stood = true;
-    if (track) return miss_after_batch(w, s, d, u, ndep, bufs, need, need_ctx, grow, st, out, err, miss);
+    if (int rc = miss.swap(miss.ctx, &miss.off, &miss.ids)) { cs.err = "missing() lists"; return rc; }
+    miss.n_lists = n;
     return AD_OK;
+}
+
+int rebuild_missing_from_entries(CfkStore& cs, const CfkUpdIn& u, const uint32_t* drank)
+{
+    CfkUpdWork* w = cs.w;
+    const hipStream_t st = cs.st;
+    const uint64_t ne = cs.s.n_ent;
+    UALLOC(w->mflag, 4 * 2 * ne, false);
+    UALLOC(w->mpp, 8 * 2 * (ne + 1), false);
+    UALLOC(w->mpend, 4 * 2 * ne, false);
+    UALLOC(w->bsum, 8 * 2 * ((ne + 1023) / 1024 + 8), false);
+    k_miss_flags<<<blocks(ne), 256, 0, st>>>(ne, cs.d, w->mflag.as<uint32_t>());
+    UCHK(run_scan_arrays(w->mflag.as<uint32_t>(), w->mpp.as<uint64_t>(), ne, 2, w->bsum.as<uint64_t>(), st));
+    k_miss_scatter<<<blocks(ne), 256, 0, st>>>(ne, w->mflag.as<uint32_t>(), w->mpp.as<uint64_t>(), w->mpend.as<uint32_t>());
+    const uint32_t* dsrc = w->dsrc.as<uint32_t>();
+    const uint64_t* mpp = w->mpp.as<uint64_t>();
+    const uint32_t* mpend = w->mpend.as<uint32_t>();
+    return rebuild_missing_lists(
+        cs, ne,
+        [&](uint32_t* cnt) {
+            k_miss_build<0><<<blocks(ne), 256, 0, st>>>(cs.s, cs.d, u, dsrc, drank, mpp, mpend, cs.miss.off, cs.miss.ids, cnt,
+                                                        nullptr, nullptr);
+        },
+        [&](const uint64_t* noff, uint32_t* nids) {
+            k_miss_build<1><<<blocks(ne), 256, 0, st>>>(cs.s, cs.d, u, dsrc, drank, mpp, mpend, cs.miss.off, cs.miss.ids, nullptr,
+                                                        noff, nids);
+        });
 }
 
 // After a batch with deps (missing() maintenance on): the additions as a second batch of
 // TRANSITIVELY_KNOWN insertions (their ids already joined the dictionary with the batch), then every
 // entry's missing() rebuilt (k_miss_build). The explicit batch stands when this part fails.
-static int miss_after_batch(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const CfkUpdIn& u, uint64_t ndep,
-                            CfkDerivedBufs* bufs, int (*need)(void*, uint64_t, uint64_t, uint64_t, CfkDerivedBufs*),
-                            void* need_ctx, const CfkGrow& grow, hipStream_t st, CfkUpdOut* out, std::string* err,
-                            CfkMiss* miss)
+static int miss_after_batch(CfkStore& cs, const CfkUpdIn& u, uint64_t ndep, CfkUpdOut* out)
 {
+    CfkUpdWork* w = cs.w;
+    DevSnapshot& s = cs.s;
+    const hipStream_t st = cs.st;
     const uint64_t n = u.n;
     UpdCtl* ctl = w->ctl.as<UpdCtl>();
     const uint8_t* uapp = w->uapp.as<uint8_t>();
-    auto dsample = [&]() -> DictSample {
-        const uint64_t n_samp = (s.n_dict + SAMP - 1) / SAMP;
-        UALLOC_V(w->sm_hi, 8 * std::max<uint64_t>(n_samp, 1));
-        UALLOC_V(w->sm_lo, 8 * std::max<uint64_t>(n_samp, 1));
-        UALLOC_V(w->sm_node, 4 * std::max<uint64_t>(n_samp, 1));
-        if (n_samp)
-            k_dict_sample<<<blocks(n_samp), 256, 0, st>>>(s, w->sm_hi.as<uint64_t>(), w->sm_lo.as<uint64_t>(),
-                                                          w->sm_node.as<int32_t>(), n_samp);
-        return DictSample{w->sm_hi.as<uint64_t>(), w->sm_lo.as<uint64_t>(), w->sm_node.as<int32_t>(), n_samp};
-    };
     // ---- additions (computeInfoAndAdditions :210-263, insertOrUpdateWithAdditions)
     UALLOC(w->drank, 4 * std::max<uint64_t>(ndep, 1), false);
     UALLOC(w->acnt, 4 * n, false);
     UALLOC(w->aoff, 8 * (n + 1), false);
     UALLOC(w->bsum, 8 * ((n + 1023) / 1024 + 8), false);
-    {
-        const DictSample ds = dsample();
-        if (ndep) k_dep_rank<<<blocks(ndep), 256, 0, st>>>(s, ds, u, ndep, w->drank.as<uint32_t>());
-    }
+    DictSample ds;
+    if (int rc = dict_sample(cs, &ds)) return rc;
+    if (ndep) k_dep_rank<<<blocks(ndep), 256, 0, st>>>(s, ds, u, ndep, w->drank.as<uint32_t>());
     // byId's last txnId per update as the sequential Java sees it (k_past_*)
     UALLOC(w->pk, 8 * n, false);
     UALLOC(w->pv, 4 * n, false);
@@ -2236,7 +2042,7 @@ static int miss_after_batch(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const
         char b[200];
         snprintf(b, sizeof(b), "cfk update %u: a dep its kind does not witness, absent from byId, is not an "
                                "ExclusiveSyncPoint (Updating.java:239-249)", w->h_ctl->err_idx);
-        *err = b;
+        cs.err = b;
         out->failed_update = w->h_ctl->err_idx;
         UCHK(hipMemsetAsync(ctl, 0, sizeof(UpdCtl), st));
         return AD_E_INVAL;
@@ -2273,14 +2079,17 @@ static int miss_after_batch(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const
                     w->a_tm.as<uint64_t>(), w->a_tl.as<uint64_t>(), w->a_tn.as<int32_t>(), w->a_st.as<uint8_t>(),
                     nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         CfkUpdOut o2;
-        if (int rc = run_cfk_update(w, s, d, ua, bufs, need, need_ctx, grow, st, &o2, err, nullptr))
+        cs.miss.on = false;       // plain insertions: the lists are rebuilt below, once
+        const int rc = run_cfk_update(cs, ua, &o2);
+        cs.miss.on = true;
+        if (rc)
         {
-            *err = "deps-derived additions: " + *err;
+            cs.err = "deps-derived additions: " + cs.err;
             return rc;
         }
         if (o2.merged || o2.n_new_ids || o2.n_new_keys)
         {
-            *err = "deps-derived additions grew the dictionary (internal: merged " + std::to_string((int)o2.merged) + ", new ids " +
+            cs.err = "deps-derived additions grew the dictionary (internal: merged " + std::to_string((int)o2.merged) + ", new ids " +
                    std::to_string(o2.n_new_ids) + ", new keys " + std::to_string(o2.n_new_keys) + ")";
             return AD_E_STATE;
         }
@@ -2294,196 +2103,233 @@ static int miss_after_batch(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const
     const uint64_t ne = s.n_ent;
     if (!ne) return AD_OK;
     UALLOC(w->dsrc, 4 * ne, false);
-    UALLOC(w->mflag, 4 * 2 * ne, false);
-    UALLOC(w->mpp, 8 * 2 * (ne + 1), false);
-    UALLOC(w->mpend, 4 * 2 * ne, false);
-    UALLOC(w->mcnt, 4 * ne, false);
-    UALLOC(w->moff, 8 * (ne + 1), false);
-    UALLOC(w->bsum, 8 * 2 * ((ne + 1023) / 1024 + 8), false);
     UCHK(hipMemsetAsync(w->dsrc.p, 0xFF, 4 * ne, st));
+    if (int rc = dict_sample(cs, &ds)) return rc;
+    k_miss_src<<<blocks(n), 256, 0, st>>>(s, ds, u, uapp, w->dsrc.as<uint32_t>());
+    return rebuild_missing_from_entries(cs, u, w->drank.as<uint32_t>());
+}
+
+int run_cfk_update(CfkStore& cs, const CfkUpdIn& u, CfkUpdOut* out)
+{
+    CfkUpdWork* w = cs.w;
+    DevSnapshot& s = cs.s;
+    CfkDevState& d = cs.d;
+    const CfkGrow& grow = cs.grow;
+    const hipStream_t st = cs.st;
+    const uint64_t n = u.n;
+    *out = CfkUpdOut{};
+    if (n == 0) return AD_OK;
+    // missing() maintenance (with the deps of the batch): the updates fold in batch order, so each
+    // update knows whether it applied and which one an entry's TxnInfo comes from
+    const bool track = cs.miss.on && u.dep_off && d.mref;
+    uint64_t ndep = 0;
+    if (track)
     {
-        const DictSample ds = dsample();
-        k_miss_src<<<blocks(n), 256, 0, st>>>(s, ds, u, uapp, w->dsrc.as<uint32_t>());
+        dev_quiesce();
+        if (d2h(&ndep, u.dep_off + n, 8, dev_scope_stream()) != hipSuccess) { cs.err = "dep_off"; return AD_E_DEVICE; }
+        UALLOC(w->uapp, n, false);
+        UCHK(hipMemsetAsync(w->uapp.p, 0, n, st));
     }
-    k_miss_flags<<<blocks(ne), 256, 0, st>>>(ne, d, w->mflag.as<uint32_t>());
-    UCHK(run_scan_arrays(w->mflag.as<uint32_t>(), w->mpp.as<uint64_t>(), ne, 2, w->bsum.as<uint64_t>(), st));
-    k_miss_scatter<<<blocks(ne), 256, 0, st>>>(ne, w->mflag.as<uint32_t>(), w->mpp.as<uint64_t>(), w->mpend.as<uint32_t>());
-    k_miss_build<0><<<blocks(ne), 256, 0, st>>>(s, d, u, w->dsrc.as<uint32_t>(), w->drank.as<uint32_t>(), w->mpp.as<uint64_t>(),
-                                                w->mpend.as<uint32_t>(), miss->off, miss->ids, w->mcnt.as<uint32_t>(), nullptr,
-                                                nullptr);
-    UCHK(run_scan_arrays(w->mcnt.as<uint32_t>(), w->moff.as<uint64_t>(), ne, 1, w->bsum.as<uint64_t>(), st));
-    uint64_t nm = 0;
-    UCHK(d2h(&nm, w->moff.as<uint64_t>() + ne, 8, st));
-    UCHK(hipStreamSynchronize(st));
-    uint64_t* noff = nullptr;
-    uint32_t* nids = nullptr;
-    if (int rc = miss->spare(miss->ctx, ne, nm, &noff, &nids)) { *err = "missing() lists"; return rc; }
-    UCHK(hipMemcpyAsync(noff, w->moff.p, 8 * (ne + 1), hipMemcpyDeviceToDevice, st));
-    k_miss_build<1><<<blocks(ne), 256, 0, st>>>(s, d, u, w->dsrc.as<uint32_t>(), w->drank.as<uint32_t>(), w->mpp.as<uint64_t>(),
-                                                w->mpend.as<uint32_t>(), miss->off, miss->ids, nullptr, noff, nids);
-    k_mref_identity<<<blocks(ne), 256, 0, st>>>(ne, d.mref);
+    if (n >= 0x7FFFFFFFull) { cs.err = "more than 2^31-2 updates in one batch"; return AD_E_INVAL; }
+    auto describe = [&](uint32_t code, uint32_t idx) -> int {
+        char b[256];
+        const char* what = "";
+        int rc = AD_E_INVAL;
+        switch (code)
+        {
+            case UE_KEY: what = "key missing from the key arrays after its creation (internal)"; rc = AD_E_STATE; break;
+            case UE_STATUS: what = "status is not an InternalStatus ordinal"; break;
+            case UE_ABSENT: what = "txnId missing from the id dictionary after its merge (internal)"; rc = AD_E_STATE; break;
+            case UE_NEW_EXEC: what = "executeAt missing from the id dictionary after its merge (internal)"; rc = AD_E_STATE; break;
+            case UE_FLAGS: what = "ids equal under Timestamp.equals differ in flag bits"; rc = AD_E_INCONSISTENT_ID; break;
+            case UE_DOMAIN: what = "live range-domain TxnId in a CommandsForKey"; break;
+            case UE_DUP_EXEC: what = "two committed entries of one key share an executeAt (CommandsForKey.java:1439)"; rc = AD_E_DUP_EXEC; break;
+        }
+        snprintf(b, sizeof(b), "cfk update %u: %s", idx, what);
+        cs.err = b;
+        return rc;
+    };
+    UALLOC(w->loc, 4 * n, false);
+    UALLOC(w->xr, 4 * n, false);
+    UALLOC(w->bk, 8 * n, false);
+    UALLOC(w->ins_k, 8 * n, false);
+    UALLOC(w->ins_v, 4 * n, false);
+    UALLOC(w->word, 8 * std::max<uint64_t>(s.n_ent, 1), true);   // zero between batches (winners clear theirs)
+    if (int rc = cfk_begin(cs)) return rc;
+    UpdCtl* ctl = w->ctl.as<UpdCtl>();
+    // per-entry changed flags of this batch (incremental committed order) and no insertion map yet
+    UALLOC(w->chg[w->chg_cur], std::max<uint64_t>(s.n_ent, 1), false);
+    if (s.n_ent) UCHK(hipMemsetAsync(w->chg[w->chg_cur].p, 0, s.n_ent, st));
+    w->moved = false;
+
+    // ---- 0. ids the dictionary does not hold join it. Ids newer than all of it are appended (no
+    // rank changes): a batch that then fails drops them again (the arrays keep the bytes; nothing
+    // refers to them). Older ones are merged with a rank remap of every stored rank: the merge
+    // stands when the batch then fails (it changes no content), and the derived arrays are rebuilt.
+    const uint64_t nd0 = s.n_dict, lh0 = s.dict_last_hi, ll0 = s.dict_last_lo;
+    const int32_t ln0 = s.dict_last_node;
+    auto drop_new_ids = [&](int code) -> int {
+        if (out->merged) return code;
+        s.n_dict = nd0;
+        s.dict_last_hi = lh0;
+        s.dict_last_lo = ll0;
+        s.dict_last_node = ln0;
+        out->n_new_ids = 0;
+        return code;
+    };
+    // the sample buffers, reserved for the 2 n ids the batch may add: the second sample does not reallocate
+    UALLOC(w->sm_hi, 8 * std::max<uint64_t>((s.n_dict + n + n + SAMP - 1) / SAMP, 1), false);
+    UALLOC(w->sm_lo, 8 * std::max<uint64_t>((s.n_dict + n + n + SAMP - 1) / SAMP, 1), false);
+    UALLOC(w->sm_node, 4 * std::max<uint64_t>((s.n_dict + n + n + SAMP - 1) / SAMP, 1), false);
+    // a derivation whose failure is appended to the message that stands (the cause of the undo)
+    auto derive_again = [&](const char* what) -> int {
+        std::string first;
+        first.swap(cs.err);
+        const int rc2 = cfk_derive(cs);
+        cs.err = rc2 ? first + what + cs.err : first;
+        return rc2;
+    };
+    // a failure after a merge or new keys: the entries are as they were, under the new ranks /
+    // key indices; derive again
+    auto rederive = [&](int code) -> int {
+        if (!out->merged && !out->n_new_keys) return code;
+        if (hipMemsetAsync(ctl, 0, sizeof(UpdCtl), st) != hipSuccess) { cs.err += "; re-derivation failed"; return AD_E_DEVICE; }
+        if (int rc2 = derive_again("; re-derivation: ")) return rc2;
+        if (hipStreamSynchronize(st) != hipSuccess) { cs.err += "; re-derivation failed"; return AD_E_DEVICE; }
+        out->rederived = true;
+        return code;
+    };
+    if (int rc = add_keys(cs, u, out)) return rc == AD_E_CAPACITY ? rc : rederive(rc);
+    host_trace("upd: add_keys");
+    if (out->n_new_keys) UCHK(hipMemsetAsync(ctl, 0, sizeof(UpdCtl), st));
+    DictSample dsm;
+    if (int rc = dict_sample(cs, &dsm)) return rederive(rc);
+    if (int rc = grow_dictionary(cs, dsm, u, out, ndep)) return rc == AD_E_CAPACITY ? drop_new_ids(rc) : rederive(rc);
+    if (w->h_ctl->err) return rederive(drop_new_ids(describe(w->h_ctl->err, w->h_ctl->err_idx)));
+
+    // ---- 1. locate and validate; nothing changes unless the whole batch is valid
+    if (int rc = dict_sample(cs, &dsm)) return rederive(drop_new_ids(rc));
+    const bool bm = u.bal_msb != nullptr;
+    const bool fold = bm || track;
+    const int nf = fold ? 2 : 1;
+    if (track) UALLOC(w->trk, 4ull * 3 * n, false);
+    UALLOC(w->uflag, 4ull * 2 * n, false);
+    UALLOC(w->upos, 8ull * 2 * (n + 1), false);
+    UALLOC(w->bsum, 8ull * 2 * ((n + 1023) / 1024 + 8), false);
+    k_upd_locate<<<blocks(n), 256, 0, st>>>(s, dsm, d, u, w->loc.as<uint32_t>(), w->xr.as<uint32_t>(),
+                                            w->word.as<unsigned long long>(), w->ins_k.as<uint64_t>(),
+                                            w->uflag.as<uint32_t>(), w->rk.as<uint32_t>(), out->merge_pos,
+                                            out->merged ? out->n_new_ids : 0, ctl, fold ? 1 : 0,
+                                            track ? w->trk.as<uint32_t>() : nullptr);
     UCHK(hipGetLastError());
+    UCHK(run_scan_arrays(w->uflag.as<uint32_t>(), w->upos.as<uint64_t>(), n, nf, w->bsum.as<uint64_t>(), st));
+    k_drv_totals<<<1, 64, 0, st>>>(w->upos.as<uint64_t>(), n, nf, ctl->tot3);
+    UCHK(d2h(w->h_ctl, ctl, sizeof(UpdCtl), st));
     UCHK(hipStreamSynchronize(st));
-    if (int rc = miss->swap(miss->ctx, &miss->off, &miss->ids)) { *err = "missing() lists"; return rc; }
-    miss->n_lists = ne;
-    (void)ctl;
+    if (w->h_ctl->err)
+    {
+        k_upd_release<<<blocks(n), 256, 0, st>>>(n, w->loc.as<uint32_t>(), w->word.as<unsigned long long>());
+        UCHK(hipStreamSynchronize(st));
+        return rederive(drop_new_ids(describe(w->h_ctl->err, w->h_ctl->err_idx)));
+    }
+    const uint64_t q = w->h_ctl->tot3[0], mp = fold ? w->h_ctl->tot3[1] : 0, ne0 = s.n_ent;
+    // the batch's first ballots: the store's entries all hold Ballot.ZERO until now
+    if (bm && !d.ballot && ne0)
+        if (int rc = grow.ballot_init(grow.ctx, ne0, &d.ballot)) { cs.err = "ballot array"; return rederive(drop_new_ids(rc)); }
+    const uint64_t cq = std::max<uint64_t>(std::max(q, mp), 1);
+    UALLOC(w->ck, 8 * cq, false);
+    UALLOC(w->cv, 4 * cq, false);
+    UALLOC(w->ck2, 8 * cq, false);
+    UALLOC(w->cv2, 4 * cq, false);
+    UALLOC(w->bkb, sizeof(Bal) * n, false);
+    UCHK(hipMemsetAsync(w->bk.p, 0xFF, 8 * n, st));          // bk[i].x = none: nothing to roll back
+    if (fold)
+    {
+        if (mp)
+        {
+            // the present entries' updates, sorted by entry (stable: batch order within), folded
+            uint64_t* ks = w->ck.as<uint64_t>();
+            uint32_t* vs = w->cv.as<uint32_t>();
+            k_compact<<<blocks(n), 256, 0, st>>>(n, w->uflag.as<uint32_t>() + n, w->upos.as<uint64_t>() + (n + 1), nullptr,
+                                                 w->loc.as<uint32_t>(), ks, vs);
+            if (mp > 1)
+            {
+                const uint64_t hist_n = radix_hist_entries(mp);
+                UALLOC(w->hist, 4 * hist_n, false);
+                UALLOC(w->hoff, 8 * (hist_n + 1), false);
+                UALLOC(w->bsum, 8 * ((std::max(hist_n, mp) + 1023) / 1024 + 8), false);
+                uint32_t mask = 0;
+                for (uint32_t b = 0; b < bytes_of(ne0 ? ne0 - 1 : 0) && b < 4; ++b) mask |= 1u << b;
+                if (mask)
+                    UCHK(radix_sort_pairs(ks, vs, w->ck2.as<uint64_t>(), w->cv2.as<uint32_t>(), mp, mask, w->hist.as<uint32_t>(),
+                                          w->hoff.as<uint64_t>(), w->bsum.as<uint64_t>(), st, &ks, &vs));
+            }
+            k_fold_present<<<blocks(mp), 256, 0, st>>>(mp, ks, vs, u, w->xr.as<uint32_t>(), d, w->bk.as<uint2>(),
+                                                       w->bkb.as<Bal>(), w->chg[w->chg_cur].as<uint8_t>(), ctl,
+                                                       track ? w->uapp.as<uint8_t>() : nullptr);
+        }
+    }
+    else
+        k_upd_apply<<<blocks(n), 256, 0, st>>>(n, w->loc.as<uint32_t>(), w->xr.as<uint32_t>(), w->word.as<unsigned long long>(),
+                                               d, w->bk.as<uint2>(), w->bkb.as<Bal>(), w->chg[w->chg_cur].as<uint8_t>(), ctl);
+    UCHK(hipGetLastError());
+    if (q)   // the insertion updates in batch order, for insert_entries
+        k_compact<<<blocks(n), 256, 0, st>>>(n, w->uflag.as<uint32_t>(), w->upos.as<uint64_t>(), w->ins_k.as<uint64_t>(),
+                                             nullptr, w->ck.as<uint64_t>(), w->cv.as<uint32_t>());
+    // From here on the per-entry state has changed: every failure undoes the batch (status and
+    // executeAt restored, insertions swapped back, krec restored) and derives the previous state
+    // again, so that nothing changes unless the whole batch is applied.
+    InsUndo undo;
+    auto rollback = [&](int code) -> int {
+        if (undo.swapped)
+        {
+            if (grow.swap(grow.ctx, ne0, &d.ent, &d.status, &d.xrank, &d.ekey, &d.ballot, &d.mref)) { cs.err += "; rollback failed"; return AD_E_DEVICE; }
+            s.ent = d.ent;
+            s.n_ent = ne0;
+        }
+        if (undo.krec_saved && s.n_keys)
+            if (hipMemcpyAsync(d.krec, w->krec_bk.p, sizeof(KeyRec) * s.n_keys, hipMemcpyDeviceToDevice, st) != hipSuccess)
+            { cs.err += "; rollback failed"; return AD_E_DEVICE; }
+        k_upd_rollback<<<blocks(n), 256, 0, st>>>(n, w->loc.as<uint32_t>(), w->bk.as<uint2>(), w->bkb.as<Bal>(), d);
+        if (hipGetLastError() != hipSuccess || hipMemsetAsync(ctl, 0, sizeof(UpdCtl), st) != hipSuccess)
+        { cs.err += "; rollback failed"; return AD_E_DEVICE; }
+        if (int rc2 = derive_again("; rollback: ")) return rc2;
+        if (hipStreamSynchronize(st) != hipSuccess) { cs.err += "; rollback failed"; return AD_E_DEVICE; }
+        out->n_applied = out->n_inserted = 0;
+        out->rolled_back = true;
+        return drop_new_ids(code);
+    };
+    uint64_t G = 0;
+    if (q)
+        if (int rc = insert_entries(cs, u, q, &G, &undo, fold, track ? w->uapp.as<uint8_t>() : nullptr))
+            return rollback(rc);
+    UCHK(hipEventRecord(w->ev[1], st));
+
+    // ---- 2. re-derive the snapshot arrays from the per-entry state (committed order incrementally)
+    if (int rc = cfk_derive(cs, true)) return rollback(rc);
+    UCHK(hipEventRecord(w->ev[2], st));
+    UCHK(d2h(w->h_ctl, ctl, sizeof(UpdCtl), st));
+    UCHK(hipStreamSynchronize(st));
+    host_trace("upd: derive sync");
+    float a = 0, b = 0;
+    (void)hipEventElapsedTime(&a, w->ev[0], w->ev[1]);
+    (void)hipEventElapsedTime(&b, w->ev[1], w->ev[2]);
+    out->ms_locate = a;
+    out->ms_derive = b;
+    out->ms_total = a + b;
+    out->n_applied = w->h_ctl->applied + G;
+    out->n_inserted = G;
+    // a duplicate committed executeAt: undo the batch and derive the previous state again
+    if (w->h_ctl->err) return rollback(describe(w->h_ctl->err, w->h_ctl->err_idx));
+    out->batch_stood = true;
+    if (track) return miss_after_batch(cs, u, ndep, out);
     return AD_OK;
 }
 
-
-// =============================================================================================
-// Pruning.maybePrune (Pruning.java:164-199) and pruneBefore (:205-331) for a list of keys, on the
-// device state. The store's TxnInfo.missing() lists are NO_TXNIDS in this model (the caller checks
-// none are loaded), so pruneBefore removes, below the new prunedBefore's byId position, every
-// INVALID_OR_TRUNCATED entry and every APPLIED entry executing before it; nothing else moves.
-// =============================================================================================
+// ---- entries leaving (cfk_trim.hip's pruning and truncation): the steps that use this file's kernels ----
 namespace {
 
-// Timestamp.hlc() of dictionary rank r (Timestamp.java:129-131: highHlc(msb) | lowHlc(lsb); the
-// normalised lo holds lowHlc << 4)
-__device__ __forceinline__ int64_t rank_hlc(const DevSnapshot& s, uint32_t r)
-{
-    const uint64_t i = (r - 1) >> 1;
-    return (int64_t)(((s.dict_hi[i] & 0x7FFFull) << 48) | (s.dict_lo[i] >> 4));
-}
-
-__global__ void k_prune_cflag(uint64_t ne, const uint8_t* status, uint32_t* f)
-{
-    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= ne) return;
-    f[e] = (status[e] >= AD_ST_COMMITTED && status[e] <= AD_ST_APPLIED) ? 1u : 0u;
-}
-
-// thread per listed key: the new prunedBefore (maybePrune :166-189) -> p_pos[k] = its byId position
-// (0: no prune), p_xr / p_tr = its executeAt / txnId ranks. cm: the committed entries sorted by
-// (key, executeAt) (committedByExecuteAt of every key, :651-672); cpos: committed entries before e.
-__global__ void k_prune_key(uint64_t nl, const uint32_t* klist, DevSnapshot s, CfkDevState d, const uint32_t* cm,
-                            const uint64_t* cpos, int32_t prune_interval, int64_t min_hlc_delta, uint32_t* p_pos,
-                            uint32_t* p_xr, uint32_t* p_tr)
-{
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= nl) return;
-    const uint32_t k = klist ? klist[t] : (uint32_t)t;
-    const KeyRec kr = d.krec[k];
-    if (kr.maw < 0) return;                                   // no APPLIED Write: maxAppliedWrite = -1
-    const uint64_t c_lo = cpos[kr.seg_lo], c_hi = cpos[kr.seg_hi];
-    // maxAppliedWriteByExecuteAt as an index into the key's committedByExecuteAt
-    const uint32_t mx = s.w[kr.maw].x;
-    uint64_t lo = c_lo, hi = c_hi;
-    while (lo < hi)
-    {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (d.xrank[cm[mid]] < mx) lo = mid + 1;
-        else hi = mid;
-    }
-    const int64_t maw = (int64_t)(lo - c_lo);
-    if (maw < (int64_t)prune_interval) return;
-    const int64_t max_prune_hlc = rank_hlc(s, mx) - min_hlc_delta;
-    int64_t i = maw;
-    uint32_t e = 0;
-    while (--i >= 0)
-    {
-        e = cm[c_lo + (uint64_t)i];
-        const uint32_t kind = d.ent[e].y >> RANK_BITS;
-        if (kind == AD_KIND_WRITE && rank_hlc(s, d.xrank[e]) <= max_prune_hlc && d.status[e] == AD_ST_APPLIED) break;
-    }
-    if (i < 0) return;
-    const uint32_t tr = d.ent[e].y & RANK_MASK;
-    if (kr.pruned && tr <= kr.pruned) return;                 // newPrunedBefore <= prunedBefore (:184)
-    const uint32_t pos = e - kr.seg_lo;                       // insertPos: it is in byId
-    if (pos == 0) return;
-    p_pos[k] = pos;
-    p_xr[k] = d.xrank[e];
-    p_tr[k] = tr;
-}
-
-// thread per entry: removed by pruneBefore (:222-254). With missing() lists on the device (d.mref)
-// the APPLIED entries are k_prune_subset's to decide; INVALID ones always go.
-__global__ void k_prune_mark(uint64_t ne, CfkDevState d, const uint32_t* p_pos, const uint32_t* p_xr, uint32_t* rm)
-{
-    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= ne) return;
-    const uint32_t k = d.ekey[e];
-    const uint32_t pos = p_pos[k];
-    bool r = false;
-    if (pos && e - d.krec[k].seg_lo < pos)
-    {
-        const uint32_t st = d.status[e];
-        r = st == AD_ST_INVALID_OR_TRUNCATED_OR_UNMANAGED_COMMITTED || (!d.mref && st == AD_ST_APPLIED && d.xrank[e] < p_xr[k]);
-    }
-    rm[e] = r ? 1u : 0u;
-}
-
-// thread per pruned key, with missing() lists (:222-251): walking byId below the new prunedBefore,
-// an APPLIED entry executing before it goes when its missing() is empty or inside the merged set --
-// the new prunedBefore's list united with the lists of the APPLIED entries kept before it that
-// execute at their txnId (the set is not built: the kept entries' indices go to `sc`, each id is
-// searched in their lists).
-__device__ inline bool list_has(const uint64_t* off, const uint32_t* ids, uint32_t L, uint32_t r)
-{
-    if (L == MREF_NONE || L == MREF_BORN) return false;
-    uint64_t lo = off[L], hi = off[L + 1];
-    while (lo < hi)
-    {
-        const uint64_t m = (lo + hi) >> 1;
-        if (ids[m] < r) lo = m + 1;
-        else hi = m;
-    }
-    return lo < off[L + 1] && ids[lo] == r;
-}
-
-__global__ void k_prune_subset(uint64_t nl, const uint32_t* klist, CfkDevState d, const uint32_t* p_pos, const uint32_t* p_xr,
-                               const uint64_t* moff, const uint32_t* mids, uint32_t* sc, uint32_t* rm)
-{
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= nl) return;
-    const uint32_t k = klist ? klist[t] : (uint32_t)t;
-    const uint32_t pos = p_pos[k];
-    if (!pos) return;
-    const uint32_t lo = d.krec[k].seg_lo, npb = lo + pos, x_npb = p_xr[k];
-    const uint32_t L0 = d.mref[npb];
-    uint32_t nret = 0;
-    for (uint32_t e = lo; e < npb; ++e)
-    {
-        if (d.status[e] != AD_ST_APPLIED || d.xrank[e] >= x_npb) continue;
-        const uint32_t L = d.mref[e];
-        bool subset = true;
-        if (L != MREF_NONE && L != MREF_BORN)
-            for (uint64_t j = moff[L]; j < moff[L + 1] && subset; ++j)
-            {
-                const uint32_t r = mids[j];
-                bool in = list_has(moff, mids, L0, r);
-                for (uint32_t q = 0; q < nret && !in; ++q) in = list_has(moff, mids, d.mref[sc[lo + q]], r);
-                subset = in;
-            }
-        if (subset)
-        {
-            rm[e] = 1u;
-            continue;
-        }
-        if (d.xrank[e] == (d.ent[e].y & RANK_MASK)) sc[lo + nret++] = e;
-    }
-}
-
-// thread per key: segments after the removals; prunedBefore where entries went (:255-257: a key
-// without removals keeps its CommandsForKey, prunedBefore included)
-__global__ void k_prune_keys(uint64_t nk, KeyRec* krec, const uint64_t* rpos, const uint32_t* p_pos, const uint32_t* p_tr,
-                             unsigned long long* n_keys_pruned)
-{
-    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= nk) return;
-    KeyRec kr = krec[k];
-    const uint64_t r_lo = rpos[kr.seg_lo], r_hi = rpos[kr.seg_hi];
-    if (p_pos[k] && r_hi > r_lo)
-    {
-        kr.pruned = p_tr[k];
-        atomicAdd(n_keys_pruned, 1ull);
-    }
-    kr.seg_lo -= (uint32_t)r_lo;
-    kr.seg_hi -= (uint32_t)r_hi;
-    krec[k] = kr;
-}
-
+// the kept entries move down by the removed ones before them
 __global__ __launch_bounds__(256) void k_prune_move(uint64_t ne, EntArrays a, const uint32_t* rm, const uint64_t* rpos,
                                                     EntArrays b)
 {
@@ -2496,358 +2342,6 @@ __global__ __launch_bounds__(256) void k_prune_move(uint64_t ne, EntArrays a, co
     b.ekey[j] = a.ekey[e];
     if (a.bal) b.bal[j] = a.bal[e];
     if (a.mref) b.mref[j] = a.mref[e];
-}
-
-}  // namespace
-
-// A freshly ingested snapshot (ingest.hip): every derived array from the per-entry state, the
-// committed order sorted in full.
-int run_cfk_derive_full(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, CfkDerivedBufs* bufs,
-                        int (*need)(void* ctx, uint64_t cand, uint64_t cwr, uint64_t w, CfkDerivedBufs* bufs), void* need_ctx,
-                        hipStream_t st, uint64_t* bad_entry, std::string* err)
-{
-    if (!w->h_ctl && hipHostMalloc((void**)&w->h_ctl, sizeof(UpdCtl)) != hipSuccess) { *err = "pinned ctl"; return AD_E_NOMEM; }
-    UALLOC(w->ctl, sizeof(UpdCtl), false);
-    UCHK(hipMemsetAsync(w->ctl.p, 0, sizeof(UpdCtl), st));
-    w->cm_valid = false;
-    w->moved = false;
-    if (int rc = cfk_derive(w, s, d, bufs, need, need_ctx, st, err)) return rc;
-    UCHK(d2h(w->h_ctl, w->ctl.p, sizeof(UpdCtl), st));
-    UCHK(hipStreamSynchronize(st));
-    if (w->h_ctl->err)
-    {
-        *bad_entry = w->h_ctl->err_idx;
-        *err = "two committed entries of one key share an executeAt (CommandsForKey.java:1439)";
-        return AD_E_DUP_EXEC;
-    }
-    return AD_OK;
-}
-
-int run_cfk_prune(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const uint32_t* klist, uint64_t nl, int32_t prune_interval,
-                  int64_t min_hlc_delta, CfkDerivedBufs* bufs,
-                  int (*need)(void* ctx, uint64_t cand, uint64_t cwr, uint64_t w, CfkDerivedBufs* bufs), void* need_ctx,
-                  const CfkGrow& grow, hipStream_t st, CfkPruneOut* out, std::string* err, CfkMiss* miss)
-{
-    *out = CfkPruneOut{};
-    const uint64_t ne = s.n_ent, nk = s.n_keys;
-    if (!nk || !ne || !nl) return AD_OK;
-    if (!w->h_ctl && hipHostMalloc((void**)&w->h_ctl, sizeof(UpdCtl)) != hipSuccess) { *err = "pinned ctl"; return AD_E_NOMEM; }
-    for (auto& e : w->ev)
-        if (!e) UCHK(timing_event(&e));
-    UALLOC(w->ctl, sizeof(UpdCtl), false);
-    UpdCtl* ctl = w->ctl.as<UpdCtl>();
-    UCHK(hipMemsetAsync(ctl, 0, sizeof(UpdCtl), st));
-    UCHK(hipEventRecord(w->ev[0], st));
-    // the committed order of the current entries (a derivation keeps it; after the ingest, derive once)
-    if (!w->cm_valid)
-    {
-        UALLOC(w->chg[w->chg_cur], ne, false);
-        w->moved = false;
-        if (int rc = cfk_derive(w, s, d, bufs, need, need_ctx, st, err)) return rc;
-        UCHK(hipMemsetAsync(ctl, 0, sizeof(UpdCtl), st));
-    }
-    UALLOC(w->flags, 4 * ne, false);
-    UALLOC(w->fs, 8 * (ne + 1), false);
-    UALLOC(w->bsum, 8 * ((ne + 1023) / 1024 + 8), false);
-    UALLOC(w->maw, 4 * nk, false);          // p_pos
-    UALLOC(w->wtail, 4 * nk, false);        // p_xr
-    UALLOC(w->gkey, 4 * nk, false);         // p_tr
-    UALLOC(w->uflag, 4 * ne, false);        // rm
-    UALLOC(w->upos, 8 * (ne + 1), false);   // rpos
-    uint32_t* p_pos = w->maw.as<uint32_t>();
-    uint32_t* p_xr = w->wtail.as<uint32_t>();
-    uint32_t* p_tr = w->gkey.as<uint32_t>();
-    k_prune_cflag<<<blocks(ne), 256, 0, st>>>(ne, d.status, w->flags.as<uint32_t>());
-    UCHK(run_scan_arrays(w->flags.as<uint32_t>(), w->fs.as<uint64_t>(), ne, 1, w->bsum.as<uint64_t>(), st));
-    UCHK(hipMemsetAsync(p_pos, 0, 4 * nk, st));
-    k_prune_key<<<blocks(nl), 256, 0, st>>>(nl, klist, s, d, w->cm.as<uint32_t>(), w->fs.as<uint64_t>(), prune_interval,
-                                            min_hlc_delta, p_pos, p_xr, p_tr);
-    k_prune_mark<<<blocks(ne), 256, 0, st>>>(ne, d, p_pos, p_xr, w->uflag.as<uint32_t>());
-    const bool lists = d.mref && miss && miss->on;
-    if (lists)
-    {
-        UALLOC(w->dsrc, 4 * ne, false);       // the subset walk's kept entries (per key, in its segment)
-        k_prune_subset<<<blocks(nl), 256, 0, st>>>(nl, klist, d, p_pos, p_xr, miss->off, miss->ids, w->dsrc.as<uint32_t>(),
-                                                   w->uflag.as<uint32_t>());
-    }
-    UCHK(hipGetLastError());
-    UCHK(run_scan_arrays(w->uflag.as<uint32_t>(), w->upos.as<uint64_t>(), ne, 1, w->bsum.as<uint64_t>(), st));
-    k_drv_totals<<<1, 64, 0, st>>>(w->upos.as<uint64_t>(), ne, 1, ctl->tot2);
-    UCHK(d2h(w->h_ctl, ctl, sizeof(UpdCtl), st));
-    UCHK(hipStreamSynchronize(st));
-    const uint64_t R = w->h_ctl->tot2[0];
-    if (R == 0)
-    {
-        UCHK(hipEventRecord(w->ev[1], st));
-        UCHK(hipEventSynchronize(w->ev[1]));
-        float a = 0;
-        (void)hipEventElapsedTime(&a, w->ev[0], w->ev[1]);
-        out->ms_total = a;
-        return AD_OK;
-    }
-    // compaction into the spare per-entry arrays, segments and prunedBefore, then a full derivation
-    unsigned long long* nkp = reinterpret_cast<unsigned long long*>(&ctl->tot2[1]);
-    UCHK(hipMemsetAsync(nkp, 0, 8, st));
-    EntArrays a{d.ent, d.status, d.xrank, d.ekey, d.ballot, nullptr, d.mref}, b{};
-    if (int rc = grow.entries(grow.ctx, ne - R, &b.ent, &b.status, &b.xrank, &b.ekey, &b.bal, &b.mref)) { *err = "entry arrays"; return rc; }
-    const uint64_t padded = std::max<uint64_t>(64, (ne - R + 63) / 64 * 64);
-    if (padded > ne - R) UCHK(hipMemsetAsync(b.ent + (ne - R), 0, sizeof(uint2) * (padded - (ne - R)), st));
-    k_prune_move<<<blocks(ne), 256, 0, st>>>(ne, a, w->uflag.as<uint32_t>(), w->upos.as<uint64_t>(), b);
-    k_prune_keys<<<blocks(nk), 256, 0, st>>>(nk, d.krec, w->upos.as<uint64_t>(), p_pos, p_tr, nkp);
-    UCHK(hipGetLastError());
-    if (int rc = grow.swap(grow.ctx, ne - R, &d.ent, &d.status, &d.xrank, &d.ekey, &d.ballot, &d.mref)) { *err = "entry swap"; return rc; }
-    s.ent = d.ent;
-    s.n_ent = ne - R;
-    w->cm_valid = false;          // entry indices changed: the next derivation sorts afresh
-    w->moved = false;
-    UALLOC(w->chg[w->chg_cur], std::max<uint64_t>(ne - R, 1), false);
-    UCHK(d2h(w->h_ctl, ctl, sizeof(UpdCtl), st));
-    UCHK(hipStreamSynchronize(st));
-    out->n_keys_pruned = w->h_ctl->tot2[1];
-    out->n_removed = R;
-    UCHK(hipMemsetAsync(ctl, 0, sizeof(UpdCtl), st));
-    if (int rc = cfk_derive(w, s, d, bufs, need, need_ctx, st, err)) return rc;
-    if (lists)
-    {
-        // the kept entries' lists, compacted again (each entry its own list, pruned ones dropped)
-        const uint64_t n2 = s.n_ent;
-        UALLOC(w->dsrc, 4 * n2, false);
-        UALLOC(w->mflag, 4 * 2 * n2, false);
-        UALLOC(w->mpp, 8 * 2 * (n2 + 1), false);
-        UALLOC(w->mpend, 4 * 2 * n2, false);
-        UALLOC(w->mcnt, 4 * n2, false);
-        UALLOC(w->moff, 8 * (n2 + 1), false);
-        UALLOC(w->bsum, 8 * 2 * ((n2 + 1023) / 1024 + 8), false);
-        UCHK(hipMemsetAsync(w->dsrc.p, 0xFF, 4 * n2, st));
-        k_miss_flags<<<blocks(n2), 256, 0, st>>>(n2, d, w->mflag.as<uint32_t>());
-        UCHK(run_scan_arrays(w->mflag.as<uint32_t>(), w->mpp.as<uint64_t>(), n2, 2, w->bsum.as<uint64_t>(), st));
-        k_miss_scatter<<<blocks(n2), 256, 0, st>>>(n2, w->mflag.as<uint32_t>(), w->mpp.as<uint64_t>(), w->mpend.as<uint32_t>());
-        const CfkUpdIn none{};
-        k_miss_build<0><<<blocks(n2), 256, 0, st>>>(s, d, none, w->dsrc.as<uint32_t>(), nullptr, w->mpp.as<uint64_t>(),
-                                                    w->mpend.as<uint32_t>(), miss->off, miss->ids, w->mcnt.as<uint32_t>(),
-                                                    nullptr, nullptr);
-        UCHK(run_scan_arrays(w->mcnt.as<uint32_t>(), w->moff.as<uint64_t>(), n2, 1, w->bsum.as<uint64_t>(), st));
-        uint64_t nm = 0;
-        UCHK(d2h(&nm, w->moff.as<uint64_t>() + n2, 8, st));
-        UCHK(hipStreamSynchronize(st));
-        uint64_t* noff = nullptr;
-        uint32_t* nids = nullptr;
-        if (int rc = miss->spare(miss->ctx, n2, nm, &noff, &nids)) { *err = "missing() lists"; return rc; }
-        UCHK(hipMemcpyAsync(noff, w->moff.p, 8 * (n2 + 1), hipMemcpyDeviceToDevice, st));
-        k_miss_build<1><<<blocks(n2), 256, 0, st>>>(s, d, none, w->dsrc.as<uint32_t>(), nullptr, w->mpp.as<uint64_t>(),
-                                                    w->mpend.as<uint32_t>(), miss->off, miss->ids, nullptr, noff, nids);
-        k_mref_identity<<<blocks(n2), 256, 0, st>>>(n2, d.mref);
-        UCHK(hipGetLastError());
-        UCHK(hipStreamSynchronize(st));
-        if (int rc = miss->swap(miss->ctx, &miss->off, &miss->ids)) { *err = "missing() lists"; return rc; }
-        miss->n_lists = n2;
-    }
-    UCHK(hipEventRecord(w->ev[1], st));
-    UCHK(d2h(w->h_ctl, ctl, sizeof(UpdCtl), st));
-    UCHK(hipStreamSynchronize(st));
-    float a_ms = 0;
-    (void)hipEventElapsedTime(&a_ms, w->ev[0], w->ev[1]);
-    out->ms_total = a_ms;
-    if (w->h_ctl->err) { *err = "derivation after pruning reported an inconsistency"; return AD_E_STATE; }
-    return AD_OK;
-}
-
-
-// =============================================================================================
-// RedundantBefore on the device: SafeCommandStore.maybeTruncate (SafeCommandStore.java:165-171) ->
-// SafeCommandsForKey.updateRedundantBefore -> CommandsForKey.withRedundantBeforeAtLeast
-// (CommandsForKey.java:1317-1341). For every key, the byId entries below its RedundantBefore entry's
-// shardRedundantBefore leave and the missing() lists of the rest lose the ids below it
-// (Utils.removeRedundantMissing, Utils.java:265-275) -- both only where something left
-// (insertPos != 0); a prunedBefore at or below it becomes NO_INFO (the constructor, :646-648). The
-// watermarks are the snapshot's rb_wm ranks (dictionary members; 0 = NONE).
-// =============================================================================================
-namespace {
-
-// the RedundantBefore entry holding key x (RedundantBefore.get: a lookup over the disjoint ascending
-// entries; epochs not read), or ~0
-__device__ inline uint64_t rb_entry_holding(const DevSnapshot& s, int64_t x)
-{
-    const bool incl = s.start_inclusive != 0;
-    uint64_t lo = 0, hi = s.n_rb;
-    while (lo < hi)
-    {
-        const uint64_t m = (lo + hi) >> 1;
-        if (incl ? s.rb_start[m] <= x : s.rb_start[m] < x) lo = m + 1;
-        else hi = m;
-    }
-    if (!lo) return ~0ull;
-    return range_contains(s.start_inclusive, s.rb_start[lo - 1], s.rb_end[lo - 1], x) ? lo - 1 : ~0ull;
-}
-
-// thread per key: t_pos[k] = insertPos(shardRedundantBefore) within byId (the entries that leave),
-// t_wm[k] = its rank (0: NONE or no entry); a prunedBefore at or below it is cleared in place;
-// *n_chg counts the keys that change
-__global__ void k_trunc_key(uint64_t nk, DevSnapshot s, KeyRec* krec, uint32_t* t_pos, uint32_t* t_wm,
-                            unsigned long long* n_chg)
-{
-    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= nk) return;
-    uint32_t pos = 0, wm = 0;
-    const uint64_t e = rb_entry_holding(s, s.keys[k]);
-    if (e != ~0ull) wm = s.rb_wm[e];
-    bool chg = false;
-    if (wm)
-    {
-        const KeyRec kr = krec[k];
-        uint32_t lo = kr.seg_lo, hi = kr.seg_hi;
-        while (lo < hi)
-        {
-            const uint32_t m = (lo + hi) >> 1;
-            if ((s.ent[m].y & RANK_MASK) < wm) lo = m + 1;
-            else hi = m;
-        }
-        pos = lo - kr.seg_lo;
-        chg = pos != 0;
-        if (kr.pruned && wm >= kr.pruned)
-        {
-            krec[k].pruned = 0;
-            chg = true;
-        }
-    }
-    t_pos[k] = pos;
-    t_wm[k] = wm;
-    if (chg) atomicAdd(n_chg, 1ull);
-}
-
-// byId segments from this length are searched by their wave (64 pivots a round, wave_lower_bound); shorter ones
-// by their own lane (at most 7 dependent loads). The wave takes its long keys one after the other, about two
-// dependent rounds each, so it pays only while they are few: above TRUNC_COOP_MAX long keys in a wave every lane
-// searches its own segment (log2 of the longest, in parallel). Both constants are reasoned, not measured.
-constexpr uint32_t TRUNC_COOP_MIN = 128;
-constexpr uint32_t TRUNC_COOP_MAX = 4;
-
-// k_trunc_key for the keys inside the risen spans only (ad_redundant_merge). The key array is ascending (ingest
-// checks it, new keys are merged in place), so a span holds one run of key ordinals [k0, k1): blockIdx.y walks the
-// spans, the blocks of a row stride over the span's run, lane per key. Every block of a row finds the run with
-// the same two searches (uniform loads, 2 * log2(nk) steps) -- no bounds pass and no read-back in between.
-// Sized for what a RedundantBefore.create step yields, one to a few spans (one per sub-range, more only when the
-// addition crosses entries of other watermarks): the repeated searches and the up to 64 blocks a row are noise
-// then. Thousands of tiny spans would still be correct (rows stride from 1024 spans on) but would want a bounds
-// pass and one flat grid instead.
-// t_pos / t_wm were cleared: the keys outside the spans keep 0. *n_exam counts the keys inside.
-__global__ __launch_bounds__(256) void k_trunc_spans(uint64_t nk, DevSnapshot s, const RbSpan* spans, uint64_t n_spans,
-                                                     KeyRec* krec, uint32_t* t_pos, uint32_t* t_wm,
-                                                     unsigned long long* n_chg, unsigned long long* n_exam)
-{
-    const uint32_t lane = lane_id();
-    const bool incl = s.start_inclusive != 0;
-    for (uint64_t sp = blockIdx.y; sp < n_spans; sp += gridDim.y)
-    {
-        const RbSpan span = spans[sp];
-        // keys before bound b's side of a range: key < b (StartInclusive), key <= b (EndInclusive)
-        auto ordinal = [&](int64_t b) -> uint64_t {
-            uint64_t lo = 0, hi = nk;
-            while (lo < hi)
-            {
-                const uint64_t m = (lo + hi) >> 1;
-                const int64_t x = s.keys[m];
-                if (incl ? x < b : x <= b) lo = m + 1;
-                else hi = m;
-            }
-            return lo;
-        };
-        const uint64_t k0 = ordinal(span.start), k1 = ordinal(span.end);
-        const uint64_t cnt = k1 > k0 ? k1 - k0 : 0;
-        if (blockIdx.x == 0 && threadIdx.x == 0 && cnt) atomicAdd(n_exam, (unsigned long long)cnt);
-        // block-uniform trip count: every lane of a wave reaches the ballots below
-        for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < cnt; base += (uint64_t)gridDim.x * blockDim.x)
-        {
-            const uint64_t i = base + threadIdx.x;
-            const bool on = i < cnt;
-            const uint64_t k = k0 + (on ? i : 0);
-            const KeyRec kr = krec[k];
-            uint32_t lo = kr.seg_lo, hi = kr.seg_hi;
-            const bool lng = on && hi - lo >= TRUNC_COOP_MIN;
-            const uint32_t n_lng = (uint32_t)__popcll(ballot(lng));
-            const bool coop = lng && n_lng <= TRUNC_COOP_MAX;
-            if (on && !coop)
-                while (lo < hi)
-                {
-                    const uint32_t m = (lo + hi) >> 1;
-                    if ((s.ent[m].y & RANK_MASK) < span.wm) lo = m + 1;
-                    else hi = m;
-                }
-            // long segments, one at a time by the whole wave
-            uint64_t todo = ballot(coop);
-            while (todo)
-            {
-                const int src = __ffsll((unsigned long long)todo) - 1;
-                todo &= todo - 1;
-                const uint32_t a = (uint32_t)__shfl((int)lo, src, 64), b = (uint32_t)__shfl((int)hi, src, 64);
-                const uint32_t p = (uint32_t)wave_lower_bound(
-                    a, b, [&](uint64_t x) { return s.ent[x].y & RANK_MASK; }, [&](uint32_t r) { return r < span.wm; });
-                if ((int)lane == src) lo = p;
-            }
-            const uint32_t pos = lo - kr.seg_lo;
-            bool chg = on && pos != 0;
-            if (on && kr.pruned && span.wm >= kr.pruned)
-            {
-                krec[k].pruned = 0;
-                chg = true;
-            }
-            if (on)
-            {
-                t_pos[k] = pos;
-                t_wm[k] = span.wm;
-            }
-            const uint32_t nc = (uint32_t)__popcll(ballot(chg));
-            if (lane == 0 && nc) atomicAdd(n_chg, (unsigned long long)nc);
-        }
-    }
-}
-
-// thread per entry: below its key's shardRedundantBefore (a prefix of the key's byId)
-__global__ void k_trunc_mark(uint64_t ne, const uint32_t* ekey, const KeyRec* krec, const uint32_t* t_pos, uint32_t* rm)
-{
-    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= ne) return;
-    const uint32_t k = ekey[e];
-    rm[e] = (e - krec[k].seg_lo < t_pos[k]) ? 1u : 0u;
-}
-
-// thread per key: segments after the removals (an emptied byId has no last txnId)
-__global__ void k_trunc_keys(uint64_t nk, KeyRec* krec, const uint64_t* rpos)
-{
-    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= nk) return;
-    KeyRec kr = krec[k];
-    kr.seg_lo -= (uint32_t)rpos[kr.seg_lo];
-    kr.seg_hi -= (uint32_t)rpos[kr.seg_hi];
-    if (kr.seg_hi == kr.seg_lo) kr.last_txn = 0;
-    krec[k] = kr;
-}
-
-// thread per kept entry (its list mref[j] of the old CSR): the ids at or above the key's
-// shardRedundantBefore where entries left (removeRedundantMissing), all of them elsewhere. Pass 0
-// counts, pass 1 writes.
-template <int WRITE>
-__global__ __launch_bounds__(256) void k_trunc_miss(uint64_t n, const uint32_t* mref, const uint32_t* ekey,
-                                                    const uint32_t* t_pos, const uint32_t* t_wm, const uint64_t* ooff,
-                                                    const uint32_t* oids, uint32_t* cnt, const uint64_t* noff, uint32_t* nids)
-{
-    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const uint32_t L = mref[j];
-    uint64_t c = 0, o = WRITE ? noff[j] : 0;
-    if (L != MREF_NONE && L != MREF_BORN)
-    {
-        const uint32_t k = ekey[j];
-        const uint32_t lb = t_pos[k] ? t_wm[k] : 0;
-        for (uint64_t a = ooff[L]; a < ooff[L + 1]; ++a)
-        {
-            const uint32_t r = oids[a];
-            if (r < lb) continue;
-            if (WRITE) nids[o++] = r;
-            ++c;
-        }
-    }
-    if (!WRITE) cnt[j] = (uint32_t)c;
 }
 
 // thread per id: its dictionary rank (a member after run_cfk_dict_ensure); a miss flags ctl->err
@@ -2865,158 +2359,83 @@ __global__ void k_id_ranks(DevSnapshot s, DictSample ds, uint64_t n, const uint6
 
 }  // namespace
 
-int run_cfk_truncate(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, CfkDerivedBufs* bufs,
-                     int (*need)(void* ctx, uint64_t cand, uint64_t cwr, uint64_t w, CfkDerivedBufs* bufs), void* need_ctx,
-                     const CfkGrow& grow, hipStream_t st, CfkTruncOut* out, std::string* err, CfkMiss* miss,
-                     uint32_t* h_pos, const RbSpan* spans, uint64_t n_spans)
+int scan_removed(CfkStore& cs, uint64_t ne)
 {
-    *out = CfkTruncOut{};
-    const uint64_t ne = s.n_ent, nk = s.n_keys;
-    if (!nk || !s.n_rb || (spans && !n_spans)) return AD_OK;
-    if (!w->h_ctl && hipHostMalloc((void**)&w->h_ctl, sizeof(UpdCtl)) != hipSuccess) { *err = "pinned ctl"; return AD_E_NOMEM; }
-    for (auto& e : w->ev)
-        if (!e) UCHK(timing_event(&e));
-    UALLOC(w->ctl, sizeof(UpdCtl), false);
-    UpdCtl* ctl = w->ctl.as<UpdCtl>();
-    UCHK(hipMemsetAsync(ctl, 0, sizeof(UpdCtl), st));
-    UCHK(hipEventRecord(w->ev[0], st));
-    UALLOC(w->tpos, 4 * nk, false);
-    UALLOC(w->twm, 4 * nk, false);
-    uint32_t* t_pos = w->tpos.as<uint32_t>();
-    uint32_t* t_wm = w->twm.as<uint32_t>();
-    unsigned long long* n_chg = reinterpret_cast<unsigned long long*>(&ctl->tot2[1]);
-    if (spans)
-    {
-        // the keys outside the spans keep t_pos = t_wm = 0; a row of blocks per span (rows and blocks stride)
-        UCHK(hipMemsetAsync(t_pos, 0, 4 * nk, st));
-        UCHK(hipMemsetAsync(t_wm, 0, 4 * nk, st));
-        const dim3 grid(std::min(blocks(nk), 64u), (unsigned)std::min<uint64_t>(n_spans, 1024));
-        k_trunc_spans<<<grid, 256, 0, st>>>(nk, s, spans, n_spans, d.krec, t_pos, t_wm, n_chg,
-                                            reinterpret_cast<unsigned long long*>(&ctl->tot3[0]));
-    }
-    else
-        k_trunc_key<<<blocks(nk), 256, 0, st>>>(nk, s, d.krec, t_pos, t_wm, n_chg);
-    if (ne)
-    {
-        UALLOC(w->uflag, 4 * ne, false);        // rm
-        UALLOC(w->upos, 8 * (ne + 1), false);   // rpos
-        UALLOC(w->bsum, 8 * ((ne + 1023) / 1024 + 8), false);
-        k_trunc_mark<<<blocks(ne), 256, 0, st>>>(ne, d.ekey, d.krec, t_pos, w->uflag.as<uint32_t>());
-        UCHK(run_scan_arrays(w->uflag.as<uint32_t>(), w->upos.as<uint64_t>(), ne, 1, w->bsum.as<uint64_t>(), st));
-        k_drv_totals<<<1, 64, 0, st>>>(w->upos.as<uint64_t>(), ne, 1, ctl->tot2);
-    }
-    UCHK(hipGetLastError());
-    UCHK(d2h(w->h_ctl, ctl, sizeof(UpdCtl), st));
-    UCHK(hipStreamSynchronize(st));
-    const uint64_t R = ne ? w->h_ctl->tot2[0] : 0, changed = w->h_ctl->tot2[1];
-    out->n_examined = spans ? w->h_ctl->tot3[0] : nk;
-    auto finish = [&]() -> int {
-        UCHK(hipEventRecord(w->ev[1], st));
-        UCHK(hipEventSynchronize(w->ev[1]));
-        float a = 0;
-        (void)hipEventElapsedTime(&a, w->ev[0], w->ev[1]);
-        out->ms_total = a;
-        return AD_OK;
-    };
-    if (!changed) return finish();
-    if (h_pos) UCHK(d2h(h_pos, t_pos, 4 * nk, st));      // the host's lists follow (the caller trims them)
-    if (R)
-    {
-        // compaction into the spare per-entry arrays and the segments, as pruning does
-        EntArrays a{d.ent, d.status, d.xrank, d.ekey, d.ballot, nullptr, d.mref}, b{};
-        if (int rc = grow.entries(grow.ctx, ne - R, &b.ent, &b.status, &b.xrank, &b.ekey, &b.bal, &b.mref)) { *err = "entry arrays"; return rc; }
-        const uint64_t padded = std::max<uint64_t>(64, (ne - R + 63) / 64 * 64);
-        if (padded > ne - R) UCHK(hipMemsetAsync(b.ent + (ne - R), 0, sizeof(uint2) * (padded - (ne - R)), st));
-        k_prune_move<<<blocks(ne), 256, 0, st>>>(ne, a, w->uflag.as<uint32_t>(), w->upos.as<uint64_t>(), b);
-        k_trunc_keys<<<blocks(nk), 256, 0, st>>>(nk, d.krec, w->upos.as<uint64_t>());
-        UCHK(hipGetLastError());
-        if (int rc = grow.swap(grow.ctx, ne - R, &d.ent, &d.status, &d.xrank, &d.ekey, &d.ballot, &d.mref)) { *err = "entry swap"; return rc; }
-        s.ent = d.ent;
-        s.n_ent = ne - R;
-        UALLOC(w->chg[w->chg_cur], std::max<uint64_t>(ne - R, 1), false);
-    }
-    if (!R)
-    {
-        // only prunedBefore moved (krec, in place): nothing derived reads it
-        out->n_keys = changed;
-        return finish();
-    }
-    w->cm_valid = false;          // entry indices changed: the next derivation sorts afresh
-    w->moved = false;
-    UCHK(hipMemsetAsync(ctl, 0, sizeof(UpdCtl), st));
-    if (int rc = cfk_derive(w, s, d, bufs, need, need_ctx, st, err)) return rc;
-    if (d.mref && miss && miss->on)
-    {
-        // the kept entries' lists, trimmed and compacted (each entry its own list again)
-        const uint64_t n2 = s.n_ent;
-        UALLOC(w->mcnt, 4 * std::max<uint64_t>(n2, 1), false);
-        UALLOC(w->moff, 8 * (n2 + 1), false);
-        UALLOC(w->bsum, 8 * ((n2 + 1023) / 1024 + 8), false);
-        if (n2)
-            k_trunc_miss<0><<<blocks(n2), 256, 0, st>>>(n2, d.mref, d.ekey, t_pos, t_wm, miss->off, miss->ids,
-                                                        w->mcnt.as<uint32_t>(), nullptr, nullptr);
-        UCHK(run_scan_arrays(w->mcnt.as<uint32_t>(), w->moff.as<uint64_t>(), n2, 1, w->bsum.as<uint64_t>(), st));
-        uint64_t nm = 0;
-        UCHK(d2h(&nm, w->moff.as<uint64_t>() + n2, 8, st));
-        UCHK(hipStreamSynchronize(st));
-        uint64_t* noff = nullptr;
-        uint32_t* nids = nullptr;
-        if (int rc = miss->spare(miss->ctx, n2, nm, &noff, &nids)) { *err = "missing() lists"; return rc; }
-        UCHK(hipMemcpyAsync(noff, w->moff.p, 8 * (n2 + 1), hipMemcpyDeviceToDevice, st));
-        if (n2)
-        {
-            k_trunc_miss<1><<<blocks(n2), 256, 0, st>>>(n2, d.mref, d.ekey, t_pos, t_wm, miss->off, miss->ids, nullptr, noff,
-                                                        nids);
-            k_mref_identity<<<blocks(n2), 256, 0, st>>>(n2, d.mref);
-        }
-        UCHK(hipGetLastError());
-        UCHK(hipStreamSynchronize(st));
-        if (int rc = miss->swap(miss->ctx, &miss->off, &miss->ids)) { *err = "missing() lists"; return rc; }
-        miss->n_lists = n2;
-    }
-    UCHK(d2h(w->h_ctl, ctl, sizeof(UpdCtl), st));
-    UCHK(hipStreamSynchronize(st));
-    if (w->h_ctl->err) { *err = "derivation after truncation reported an inconsistency"; return AD_E_STATE; }
-    out->n_removed = R;
-    out->n_keys = changed;
-    return finish();
+    CfkUpdWork* w = cs.w;
+    UALLOC(w->bsum, 8 * ((ne + 1023) / 1024 + 8), false);
+    UCHK(run_scan_arrays(w->uflag.as<uint32_t>(), w->upos.as<uint64_t>(), ne, 1, w->bsum.as<uint64_t>(), cs.st));
+    k_drv_totals<<<1, 64, 0, cs.st>>>(w->upos.as<uint64_t>(), ne, 1, w->ctl.as<UpdCtl>()->tot2);
+    return AD_OK;
 }
 
-int run_cfk_dict_ensure(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const uint64_t* msb, const uint64_t* lsb,
-                        const int32_t* node, uint64_t n, const CfkGrow& grow, CfkDerivedBufs* bufs,
-                        int (*need)(void* ctx, uint64_t cand, uint64_t cwr, uint64_t w, CfkDerivedBufs* bufs), void* need_ctx,
-                        hipStream_t st, CfkUpdOut* out, uint32_t* ranks, std::string* err)
+int compact_entries(CfkStore& cs, const uint32_t* rm, const uint64_t* rpos, uint64_t R, const std::function<void()>& per_key)
 {
+    CfkUpdWork* w = cs.w;
+    DevSnapshot& s = cs.s;
+    CfkDevState& d = cs.d;
+    const CfkGrow& grow = cs.grow;
+    const hipStream_t st = cs.st;
+    const uint64_t ne = s.n_ent;
+    EntArrays a{d.ent, d.status, d.xrank, d.ekey, d.ballot, nullptr, d.mref}, b{};
+    if (int rc = grow.entries(grow.ctx, ne - R, &b.ent, &b.status, &b.xrank, &b.ekey, &b.bal, &b.mref)) { cs.err = "entry arrays"; return rc; }
+    const uint64_t padded = std::max<uint64_t>(64, (ne - R + 63) / 64 * 64);
+    if (padded > ne - R) UCHK(hipMemsetAsync(b.ent + (ne - R), 0, sizeof(uint2) * (padded - (ne - R)), st));
+    k_prune_move<<<blocks(ne), 256, 0, st>>>(ne, a, rm, rpos, b);
+    per_key();
+    UCHK(hipGetLastError());
+    if (int rc = grow.swap(grow.ctx, ne - R, &d.ent, &d.status, &d.xrank, &d.ekey, &d.ballot, &d.mref)) { cs.err = "entry swap"; return rc; }
+    s.ent = d.ent;
+    s.n_ent = ne - R;
+    w->cm_valid = false;          // entry indices changed: the next derivation sorts afresh
+    w->moved = false;
+    UALLOC(w->chg[w->chg_cur], std::max<uint64_t>(ne - R, 1), false);
+    return AD_OK;
+}
+
+// A freshly ingested snapshot (ingest.hip): every derived array from the per-entry state, the
+// committed order sorted in full.
+int run_cfk_derive_full(CfkStore& cs, uint64_t* bad_entry)
+{
+    CfkUpdWork* w = cs.w;
+    if (int rc = cfk_begin(cs)) return rc;
+    w->cm_valid = false;
+    w->moved = false;
+    if (int rc = cfk_derive(cs)) return rc;
+    UCHK(d2h(w->h_ctl, w->ctl.p, sizeof(UpdCtl), cs.st));
+    UCHK(hipStreamSynchronize(cs.st));
+    if (w->h_ctl->err)
+    {
+        *bad_entry = w->h_ctl->err_idx;
+        cs.err = "two committed entries of one key share an executeAt (CommandsForKey.java:1439)";
+        return AD_E_DUP_EXEC;
+    }
+    return AD_OK;
+}
+
+int run_cfk_dict_ensure(CfkStore& cs, const CfkIds& ids, uint32_t* ranks, CfkUpdOut* out)
+{
+    CfkUpdWork* w = cs.w;
+    DevSnapshot& s = cs.s;
+    const hipStream_t st = cs.st;
+    const uint64_t n = ids.n;
     *out = CfkUpdOut{};
     if (!n) return AD_OK;
-    if (!w->h_ctl && hipHostMalloc((void**)&w->h_ctl, sizeof(UpdCtl)) != hipSuccess) { *err = "pinned ctl"; return AD_E_NOMEM; }
-    UALLOC(w->ctl, sizeof(UpdCtl), false);
+    if (int rc = cfk_begin(cs)) return rc;
     UpdCtl* ctl = w->ctl.as<UpdCtl>();
-    UCHK(hipMemsetAsync(ctl, 0, sizeof(UpdCtl), st));
     UALLOC(w->ids_st, n, false);
     UCHK(hipMemsetAsync(w->ids_st.p, 0, n, st));       // TRANSITIVELY_KNOWN: the txnId side only
     CfkUpdIn u{};
     u.n = n;
-    u.txn_msb = u.exec_msb = msb;
-    u.txn_lsb = u.exec_lsb = lsb;
-    u.txn_node = u.exec_node = node;
+    u.txn_msb = u.exec_msb = ids.msb;
+    u.txn_lsb = u.exec_lsb = ids.lsb;
+    u.txn_node = u.exec_node = ids.node;
     u.status = w->ids_st.as<uint8_t>();
-    const uint64_t ns = std::max<uint64_t>((s.n_dict + n + SAMP - 1) / SAMP, 1);
-    UALLOC(w->sm_hi, 8 * ns, false);
-    UALLOC(w->sm_lo, 8 * ns, false);
-    UALLOC(w->sm_node, 4 * ns, false);
-    auto sample = [&]() -> DictSample {
-        const uint64_t n_samp = (s.n_dict + SAMP - 1) / SAMP;
-        if (n_samp)
-            k_dict_sample<<<blocks(n_samp), 256, 0, st>>>(s, w->sm_hi.as<uint64_t>(), w->sm_lo.as<uint64_t>(),
-                                                          w->sm_node.as<int32_t>(), n_samp);
-        return DictSample{w->sm_hi.as<uint64_t>(), w->sm_lo.as<uint64_t>(), w->sm_node.as<int32_t>(), n_samp};
-    };
-    const DictSample ds0 = sample();
-    if (int rc = grow_dictionary(w, s, d, ds0, u, grow, st, out, err)) return rc;
+    DictSample ds;
+    if (int rc = dict_sample(cs, &ds)) return rc;
+    if (int rc = grow_dictionary(cs, ds, u, out)) return rc;
     if (w->h_ctl->err)
     {
-        *err = "ids equal under Timestamp.equals differ in flag bits";
+        cs.err = "ids equal under Timestamp.equals differ in flag bits";
         return AD_E_INCONSISTENT_ID;
     }
     if (out->merged)
@@ -3027,21 +2446,21 @@ int run_cfk_dict_ensure(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const uin
         w->moved = false;
         UALLOC(w->chg[w->chg_cur], std::max<uint64_t>(s.n_ent, 1), false);
         UCHK(hipMemsetAsync(ctl, 0, sizeof(UpdCtl), st));
-        if (int rc = cfk_derive(w, s, d, bufs, need, need_ctx, st, err)) return rc;
+        if (int rc = cfk_derive(cs)) return rc;
         out->rederived = true;
     }
-    const DictSample ds1 = sample();
+    if (int rc = dict_sample(cs, &ds)) return rc;
     UCHK(hipMemsetAsync(ctl, 0, sizeof(UpdCtl), st));
-    k_id_ranks<<<blocks(n), 256, 0, st>>>(s, ds1, n, msb, lsb, node, d.dict_lsb_raw, ranks, ctl);
+    k_id_ranks<<<blocks(n), 256, 0, st>>>(s, ds, n, ids.msb, ids.lsb, ids.node, cs.d.dict_lsb_raw, ranks, ctl);
     UCHK(hipGetLastError());
     UCHK(d2h(w->h_ctl, ctl, sizeof(UpdCtl), st));
     UCHK(hipStreamSynchronize(st));
     if (w->h_ctl->err == UE_FLAGS)
     {
-        *err = "ids equal under Timestamp.equals differ in flag bits";
+        cs.err = "ids equal under Timestamp.equals differ in flag bits";
         return AD_E_INCONSISTENT_ID;
     }
-    if (w->h_ctl->err) { *err = "id missing from the dictionary after its growth (internal)"; return AD_E_STATE; }
+    if (w->h_ctl->err) { cs.err = "id missing from the dictionary after its growth (internal)"; return AD_E_STATE; }
     return AD_OK;
 }
 

@@ -150,21 +150,32 @@ void cfk_upd_work_destroy(CfkUpdWork* w);
 // the snapshot was rebuilt outside run_cfk_update: drop state kept between batches
 void cfk_upd_work_invalidate(CfkUpdWork* w);
 
-// Applies the batch (AD_E_* on failure with the store unchanged; message in *err).
-// `need` is called with the sizes the derived arrays need; it must return buffers at least that
-// large (possibly reallocated) in *bufs.
-// With miss (non-null, on): the TxnInfo.missing() lists and the deps-derived additions follow
-// (Updating.insertOrUpdate, Updating.java:99-470): see run_cfk_update.
-int run_cfk_update(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const CfkUpdIn& u, CfkDerivedBufs* bufs,
-                   int (*need)(void* ctx, uint64_t cand, uint64_t cwr, uint64_t w, CfkDerivedBufs* bufs), void* need_ctx,
-                   const CfkGrow& grow, hipStream_t st, CfkUpdOut* out, std::string* err, CfkMiss* miss = nullptr);
+// A store as every run_cfk_* call sees it: the work area, the snapshot, the per-entry state and the
+// buffers, callbacks and lists that go with them. The calls update d, bufs and miss in place as arrays
+// are swapped or grown. `need` is called with the sizes the derived arrays need; it must return buffers
+// at least that large (possibly reallocated) in *bufs. A failing call leaves its message in err.
+struct CfkStore {
+    CfkUpdWork* w;
+    DevSnapshot& s;
+    CfkDevState d{};
+    CfkDerivedBufs bufs{};
+    int (*need)(void* ctx, uint64_t cand, uint64_t cwr, uint64_t w, CfkDerivedBufs* bufs) = nullptr;
+    void* need_ctx = nullptr;
+    CfkGrow grow{};
+    CfkMiss miss;
+    hipStream_t st = nullptr;
+    std::string err;
+};
+
+// Applies the batch (AD_E_* on failure with the store unchanged).
+// With cs.miss.on: the TxnInfo.missing() lists and the deps-derived additions follow
+// (Updating.insertOrUpdate, Updating.java:99-470).
+int run_cfk_update(CfkStore& cs, const CfkUpdIn& u, CfkUpdOut* out);
 
 // Every derived array (ent.tau, cand, cwr, w, krec's Write fields, kent, trees) of a snapshot whose
 // per-entry state was just built (ingest.hip); AD_E_DUP_EXEC with *bad_entry on a duplicate committed
 // executeAt (CommandsForKey.java:1439).
-int run_cfk_derive_full(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, CfkDerivedBufs* bufs,
-                        int (*need)(void* ctx, uint64_t cand, uint64_t cwr, uint64_t w, CfkDerivedBufs* bufs), void* need_ctx,
-                        hipStream_t st, uint64_t* bad_entry, std::string* err);
+int run_cfk_derive_full(CfkStore& cs, uint64_t* bad_entry);
 
 struct CfkPruneOut {
     uint64_t n_removed = 0;        // entries removed
@@ -173,14 +184,12 @@ struct CfkPruneOut {
 };
 
 // Pruning.maybePrune (Pruning.java:164-199 -> pruneBefore :205-331) for the keys klist[0..nl) (key
-// indices, device; null: every key, nl = n_keys); TxnInfo.missing() from miss when it is on (the
+// indices, device; null: every key, nl = n_keys); TxnInfo.missing() from cs.miss when it is on (the
 // subset test of :239-251), else NO_TXNIDS for every entry.
 // Removed entries leave the per-entry arrays (compacted into the spare buffers), the segments and
 // prunedBefore follow, and the derived arrays are rebuilt. Ids stay in the dictionary.
-int run_cfk_prune(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const uint32_t* klist, uint64_t nl, int32_t prune_interval,
-                  int64_t min_hlc_delta, CfkDerivedBufs* bufs,
-                  int (*need)(void* ctx, uint64_t cand, uint64_t cwr, uint64_t w, CfkDerivedBufs* bufs), void* need_ctx,
-                  const CfkGrow& grow, hipStream_t st, CfkPruneOut* out, std::string* err, CfkMiss* miss = nullptr);
+int run_cfk_prune(CfkStore& cs, const uint32_t* klist, uint64_t nl, int32_t prune_interval, int64_t min_hlc_delta,
+                  CfkPruneOut* out);
 
 struct CfkTruncOut {
     uint64_t n_removed = 0;        // entries removed
@@ -199,23 +208,23 @@ struct RbSpan {
 // CommandsForKey.withRedundantBeforeAtLeast (CommandsForKey.java:1317-1341) of every key to the
 // snapshot's RedundantBefore (rb_* views; watermark ranks are dictionary members): the entries below
 // the key's shardRedundantBefore leave (compacted into the spare buffers), a prunedBefore at or below
-// it is cleared, the derived arrays are rebuilt, and with miss on the kept entries' missing() lists
+// it is cleared, the derived arrays are rebuilt, and with cs.miss on the kept entries' missing() lists
 // lose the ids below it (Utils.removeRedundantMissing). h_pos (host, n_keys; may be null): each key's
 // count of removed entries, for host-held lists. spans (device, n_spans ascending disjoint; null: every key):
 // only the keys inside them are examined, each against its span's watermark -- the other keys keep theirs
 // (ad_redundant_merge: the keys whose watermark did not move were truncated to it before).
-int run_cfk_truncate(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, CfkDerivedBufs* bufs,
-                     int (*need)(void* ctx, uint64_t cand, uint64_t cwr, uint64_t w, CfkDerivedBufs* bufs), void* need_ctx,
-                     const CfkGrow& grow, hipStream_t st, CfkTruncOut* out, std::string* err, CfkMiss* miss,
-                     uint32_t* h_pos, const RbSpan* spans = nullptr, uint64_t n_spans = 0);
+int run_cfk_truncate(CfkStore& cs, uint32_t* h_pos, const RbSpan* spans, uint64_t n_spans, CfkTruncOut* out);
 
-// The ids (device arrays, n) join the dictionary where it does not hold them (appended, or merged
+// TxnIds as device columns
+struct CfkIds {
+    const uint64_t* msb; const uint64_t* lsb; const int32_t* node;
+    uint64_t n;
+};
+
+// The ids join the dictionary where it does not hold them (appended, or merged
 // with the rank remap of an update batch: out->merged / merge_pos as run_cfk_update reports them);
 // ranks[i] (device) = each id's member rank afterwards. After a merge the derived arrays are derived again
 // (out->rederived); the caller rebuilds the KeyLines (cfk_update_follow does).
-int run_cfk_dict_ensure(CfkUpdWork* w, DevSnapshot& s, CfkDevState& d, const uint64_t* msb, const uint64_t* lsb,
-                        const int32_t* node, uint64_t n, const CfkGrow& grow, CfkDerivedBufs* bufs,
-                        int (*need)(void* ctx, uint64_t cand, uint64_t cwr, uint64_t w, CfkDerivedBufs* bufs), void* need_ctx,
-                        hipStream_t st, CfkUpdOut* out, uint32_t* ranks, std::string* err);
+int run_cfk_dict_ensure(CfkStore& cs, const CfkIds& ids, uint32_t* ranks, CfkUpdOut* out);
 
 }  // namespace adx
